@@ -2,10 +2,10 @@
 """bench.py -- headline benchmark of the separable-resize hot path on MI355X.
 
 Metric (BASELINE.json): output Mpixels/s for 3840x2160 -> 7680x4320 RGBA
-float32 (cfg3) through avir::CImageResizer<>(16), plus the fraction of the HBM
-roofline achieved by the dominant kernel.
+float32 (cfg3) through avir::CImageResizer<>(16), plus (--full) the fraction of
+the HBM roofline achieved by the dominant kernel.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one full resize of one synthetic 4K frame already resident in HBM
 (H pass + V pass). N > 1 (launched by torch.distributed.run, one rank per GPU)
@@ -17,8 +17,13 @@ resize), and stitched on rank 0 with RCCL send/recv over xGMI, sub-band by
 sub-band under the kernels (avir_amd/sharding.py BandPipeline). `value` =
 stitched frames * Mpix over the max-over-ranks wall time (strong scaling). If
 the band pipeline fails, `value` is null and the exit code is 3: a line whose
-number changed meaning must not look like a success. After the timed region
+number changed meaning must not look like a success.
+
+A plain run sets up, settles the clocks, runs the W warm-up steps, times the K
+steps and prints the line. --dump-outputs DIR then also writes what the last
+timed step computed (dump_outputs()). With --full, after the timed region
 (never inside it) rank 0 also reports, in the same JSON line:
+  parity        FNV-1a-64 of the timed buffer against the reference's golden hash
   configs       (N == 1) every other BASELINE.json config that runs on one GPU
                 -- cfg1, cfg2, cfg4, cfg5 -- timed the same way: ms_per_step,
                 Mpix/s, roofline fraction, counter traffic from the committed
@@ -32,6 +37,8 @@ number changed meaning must not look like a success. After the timed region
                 gather GB/s against the xGMI link peak, and the throughput of
                 independent frames per GPU (no collective) for comparison
   sustained     the same step timed over >= 1 s (the default region is ms)
+  host_pointer_call, telemetry (N == 1)
+--no-cpu, --no-configs and --no-sustained leave single legs of --full out.
 """
 import argparse
 import ctypes as C
@@ -508,6 +515,23 @@ def traffic_provenance():
         return None
 
 
+DUMP_DRAWS = 1 << 21  # ~2.03e6 distinct pixels: ~32 MB of the 531-MB frame
+
+
+def dump_outputs(dirname, frame):
+    """Writes DIR/resized_sample.npy: float32 (n, CH), the pixels of the
+    resized frame at the sorted distinct flat indices (row * NEW_W + column)
+    among DUMP_DRAWS draws of numpy.random.default_rng(0) -- the same pixels in
+    every run, so that two builds can be compared output for output."""
+    import numpy as np
+    import torch
+    idx = np.unique(np.random.default_rng(0).integers(
+        0, NEW_H * NEW_W, DUMP_DRAWS))
+    pix = frame.reshape(-1, CH)[torch.from_numpy(idx).to(frame.device)]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "resized_sample.npy"), pix.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -520,6 +544,13 @@ def main():
     ap.add_argument("--path", type=int, default=0,
                     help="0 auto, 1 generic, 2 two-pass, 3 fused tile, 4 up2, "
                          "5 pass kernels (A/B)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the parity hash, roofline, "
+                         "sustained leg, the other configs, the host-pointer "
+                         "call, the CPU baselines and (N > 1) the sharded legs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write a fixed sample of the last timed step's frame "
+                         "to DIR/resized_sample.npy (float32)")
     ap.add_argument("--no-cpu", action="store_true",
                     help="skip the CPU baseline leg")
     ap.add_argument("--backend", default="nccl",
@@ -545,6 +576,8 @@ def main():
                     help="cfg3 (the headline, default) or one of: "
                          + ", ".join(sorted(OTHER)))
     args = ap.parse_args()
+    if args.dump_outputs and (args.report or args.workload != "cfg3"):
+        ap.error("--dump-outputs writes the headline's frame (cfg3 only)")
 
     if args.report:
         report(args.steps, args.warmup, args.settle_ms)
@@ -806,21 +839,24 @@ def main():
     if src_window is not None:
         out["config"]["source_rows_on_this_rank"] = src_window
 
-    # parity spot check on the very buffer that was timed (N > 1: the frame
-    # stitched on rank 0 in the last step)
+    # the very buffer that was timed (N > 1: the frame stitched on rank 0 in
+    # the last step): written out, and with --full its parity spot check
     if rank == 0:
         got = dst if pipe is None else pipe.frame((pipe.nframe - 1) % pipe.slots)
-        h = synth.fnv(got.cpu().numpy())
-        out["parity"] = {"fnv1a64": h, "golden": "38d7739587151f6e",
-                         "ok": h == "38d7739587151f6e"}
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, got)
+        if args.full:
+            h = synth.fnv(got.cpu().numpy())
+            out["parity"] = {"fnv1a64": h, "golden": "38d7739587151f6e",
+                             "ok": h == "38d7739587151f6e"}
 
     # ---- roofline of the dominant kernel: whole-frame launches on this
     # rank's stream (N > 1: measured after the headline, same plan)
-    if pipe is not None:
+    if args.full and pipe is not None:
         for _ in range(5):
             full_frame()
         _, ev_ms = timed(full_frame, max(20, min(args.steps, 200)))
-    if rank == 0:
+    if args.full and rank == 0:
         # One launch per step (path 4): the step IS the kernel. `frac` is priced
         # on the SAME clock as ms_per_step -- the wall time of the K timed steps
         # between the synchronisations, the number the driver's own clock can
@@ -865,7 +901,7 @@ def main():
                 "note": "instruction count from the committed PMC pass; peak "
                         "= measured packed mul+add rate of the chip"}
 
-    if world > 1 or args.pg_smoke:
+    if args.full and (world > 1 or args.pg_smoke):
         # secondary measurements: must never take the headline line down
         try:
             extra = sharded_extras(lib, plan, src, dst, dev, world, rank, dist,
@@ -887,7 +923,7 @@ def main():
         out["value_distributed"] = out["value"]
         out["value_independent_frames"] = out["value"]
 
-    if rank == 0 and world == 1 and not args.no_sustained:
+    if args.full and rank == 0 and world == 1 and not args.no_sustained:
         # a sustained figure: the default timed region is a few ms; >= 5 s
         # of back-to-back frames is also what a 1 Hz utilisation sampler sees
         n = max(args.steps, int(5.0 / max(t / args.steps, 1e-6)))
@@ -934,7 +970,8 @@ def main():
         full_frame()  # (dst holds the real frame again)
         torch.cuda.synchronize(dev)
 
-    if rank == 0 and world == 1 and not args.pg_smoke and not args.no_configs:
+    if (args.full and rank == 0 and world == 1 and not args.pg_smoke
+            and not args.no_configs):
         # every other BASELINE.json config that runs on one GPU, the same way
         # (only cfg3 used to reach the driver's line)
         out["configs"] = []
@@ -948,7 +985,7 @@ def main():
                     type(e).__name__, e)})
         out["configs_parity_ok"] = all(c.get("parity_ok") for c in out["configs"])
 
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         # the drop-in call as a host program makes it: host pointers in and
         # out, staged over PCIe inside the library. Reported
         # beside the headline, never as `value`.

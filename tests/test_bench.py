@@ -22,8 +22,8 @@ def _last_json(out):
 @gpu
 def test_bench_single_gpu_line():
     r = subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup",
-                        "2", "--settle-ms", "50", "--no-cpu"], cwd=ROOT,
-                       capture_output=True, text=True, timeout=600)
+                        "2", "--settle-ms", "50", "--no-cpu", "--full"],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     assert d["n_gpus"] == 1 and d["steps"] == 5 and d["parity"]["ok"]
@@ -43,6 +43,50 @@ def test_bench_single_gpu_line():
 
 
 @gpu
+def test_bench_plain_run_is_lean_and_dumps_the_timed_frame(tmp_path):
+    """The plain line: K timed steps and the headline fields, none of the
+    --full legs; --dump-outputs writes the documented sample of the timed
+    frame, equal bit for bit to the same pixels of the same resize."""
+    import numpy as np
+    import torch
+    import avir_amd
+    import bench
+    from avir_amd import synth
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps",
+                        "7", "--warmup", "2", "--dump-outputs", str(tmp_path)],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _last_json(r.stdout)
+    assert d["steps"] == 7 and d["ms_per_step"] > 0 and d["value"] > 0, d
+    assert d["unit"] == "Mpixels/s" and d["higher_is_better"] is True, d
+    assert d["dtype"] == "f32" and d["metric"], d
+    assert not set(d) & {"parity", "roofline", "sustained", "configs",
+                         "cpu_baseline", "host_pointer_call", "telemetry",
+                         "sharded"}, sorted(d)
+    assert os.listdir(tmp_path) == ["resized_sample.npy"]
+    got = np.load(os.path.join(tmp_path, "resized_sample.npy"))
+    assert got.dtype == np.float32 and got.nbytes <= 64 << 20, got.shape
+    idx = np.unique(np.random.default_rng(0).integers(
+        0, bench.NEW_H * bench.NEW_W, bench.DUMP_DRAWS))
+    src = torch.from_numpy(synth.lcg_f32((bench.SRC_H, bench.SRC_W,
+                                          bench.CH))).to("cuda:0")
+    full = avir_amd.CImageResizer(16).resize(src, bench.NEW_W, bench.NEW_H)
+    want = full.reshape(-1, bench.CH)[torch.from_numpy(idx).to("cuda:0")]
+    assert np.array_equal(got.view(np.uint32),
+                          want.cpu().numpy().view(np.uint32))
+
+
+def test_bench_dump_outputs_is_the_headline_only():
+    """--dump-outputs writes the headline's frame: with --workload or --report
+    it is refused before anything touches a device."""
+    for extra in (["--workload", "cfg2"], ["--report"]):
+        r = subprocess.run([sys.executable, "bench.py", "--dump-outputs", "x"]
+                           + extra, cwd=ROOT, capture_output=True, text=True,
+                           timeout=300)
+        assert r.returncode == 2 and "cfg3 only" in r.stderr, r.stderr[-500:]
+
+
+@gpu
 @pytest.mark.parametrize("world", [2, 8])
 def test_bench_two_ranks_band_pipeline_gloo_dry_run(world):
     """The driver's N > 1 command as far as one GPU can take it: `world` ranks
@@ -53,7 +97,7 @@ def test_bench_two_ranks_band_pipeline_gloo_dry_run(world):
            "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(port), "bench.py", "--gpus", str(world),
            "--steps", "3", "--warmup", "1", "--settle-ms", "0", "--backend",
-           "gloo", "--no-cpu"]
+           "gloo", "--no-cpu", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
@@ -100,7 +144,7 @@ def test_bench_one_rank_process_group_on_rccl():
                MASTER_PORT=str(29500 + os.getpid() % 150))
     r = subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup",
                         "2", "--settle-ms", "50", "--no-cpu", "--pg-smoke",
-                        "--backend", "nccl"], cwd=ROOT, env=env,
+                        "--backend", "nccl", "--full"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     d = _last_json(r.stdout)
@@ -121,7 +165,7 @@ def test_bench_gpus_2_starts_two_ranks_by_itself():
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps",
                         "3", "--warmup", "1", "--settle-ms", "0", "--backend",
-                        "gloo", "--no-cpu"], cwd=ROOT, env=env,
+                        "gloo", "--no-cpu", "--full"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     d = _last_json(r.stdout)
