@@ -32,7 +32,7 @@
 // interval A = {V of this step with H1 of the NEXT step woven into it}.
 // The horizontally resized intermediate (the reference's FltBuf) never exists
 // in memory, vertical work is never recomputed inside a chunk, and all 56
-// filter coefficients are wave-uniform SGPR pairs.
+// filter coefficients are wave-uniform scalar operands (Taps).
 //
 // Arithmetic contract: -ffp-contract=off, mul then add in the reference's tap
 // order, interpolation sums started from +0.0f => bit-identical output.
@@ -75,18 +75,37 @@ struct Up2Params
 	int dbg; // timing ablations (debug build only)
 	unsigned long long* clk; // [items][4]: shader cycles, start, end (100 MHz ticks), hw id
 #endif
-	const float* coef; // device: 2 axes x 64 floats, every tap stored twice:
-		// [f 4x2 | fe 12x2 | fo 12x2 | pad 8]; horizontal axis first
+	const float* coef; // device: the taps, horizontal axis first, packed
+		// (2 x 32 floats) and paired (2 x 64 from U2_PAIRED): see Taps
 };
 
-// The 28 wave-uniform filter taps of one axis, each held as an aligned SGPR
-// PAIR {c, c} so that v_pk_mul_f32 takes it directly as its 64-bit scalar
-// operand (no s_mov to build pairs, no op_sel games). They are loaded per phase
-// with a volatile scalar load: letting the compiler hoist both axes' taps out
-// of the marching loop overflowed the SGPR file and spilled into VGPR lanes.
+// The 28 wave-uniform filter taps of one axis, in two layouts (up2_prepare):
+//   packed (the transposed form, k_up2< true >): ONE float per tap,
+//       [f 4 | fe 12 | fo 12 | pad 4] per axis at coef + 0 / + 32. A tap enters
+//       v_pk_mul_f32 as the 64-bit scalar operand of the aligned SGPR pair it
+//       lies in, broadcast to both halves by op_sel / op_sel_hi (the compiler
+//       folds splat() below into them; for some odd taps it copies the tap
+//       into the low half of a pair of its own with one s_mov) -- half the
+//       SGPRs of the paired layout, which filled the SGPR file of this form
+//       and spilled 58 SGPRs into VGPR lanes (v_readlane in the marching loop).
+//   paired (the plain form, k_up2< false >): every tap an aligned pair {c, c},
+//       [f 4x2 | fe 12x2 | fo 12x2 | pad 8] per axis at coef + U2_PAIRED /
+//       + U2_PAIRED + 64. Its vertical phase reads all 28 vertical taps in
+//       every row; from the packed layout the compiler's s_mov copies of the
+//       odd ones cost more SGPRs than the pairs (spills 19 -> 53).
+// They are loaded per phase with a volatile scalar load: letting the compiler
+// hoist both axes' taps out of the marching loop overflowed the SGPR file.
 typedef float f8 __attribute__(( ext_vector_type( 8 )));
 typedef float f16 __attribute__(( ext_vector_type( 16 )));
+#define U2_PAIRED 64 // floats: the paired layout's offset in Up2Params::coef
 
+// (wave-uniform tap) -> the packed operand {c, c}
+__device__ __forceinline__ f2 splat( const float c )
+{
+	f2 r; r.x = c; r.y = c; return( r );
+}
+
+// the whole axis, paired (the plain form)
 struct Taps
 {
 	f16 a, b, c; // f0..3 fe0..3 | fe4..11 | fo0..7   (as pairs)
@@ -128,28 +147,56 @@ __device__ __forceinline__ Taps load_taps( const float* p0 )
 	return( t );
 }
 
-// f0..3 and fe0..11 only (the transposed vertical phase needs no fo)
+// packed fe0..11 and fo0..11 (the horizontal interpolation: 24 SGPRs)
+struct TapsI
+{
+	f16 a; // fe0..11 fo0..3
+	f8 b;  // fo4..11
+	__device__ __forceinline__ f2 fe( int i ) const { return( splat( a[ i ])); }
+	__device__ __forceinline__ f2 fo( int i ) const
+		{ return( splat( i < 4 ? a[ 12 + i ] : b[ i - 4 ])); }
+};
+
+__device__ __forceinline__ TapsI load_taps_i( const float* p0 )
+{
+	const float* const p = sgpr_ptr( p0 );
+	TapsI t;
+	asm volatile( "s_load_dwordx16 %0, %2, 0x10\n\t"
+		"s_load_dwordx8 %1, %2, 0x50\n\t"
+		AVIRHIP_WAITCNT_LGKM( 0 )
+		: "=&s"( t.a ), "=&s"( t.b ) : "s"( p ) : "memory" );
+	return( t );
+}
+
+// packed f0..3 and fe0..11 (the transposed vertical phase needs no fo)
 struct TapsE
 {
-	f16 a, b;
-	__device__ __forceinline__ f2 pr( const f16& v, int i ) const
-		{ f2 r; r.x = v[ 2 * i ]; r.y = v[ 2 * i + 1 ]; return( r ); }
-	__device__ __forceinline__ f2 f( int i ) const { return( pr( a, i )); }
-	__device__ __forceinline__ f2 fe( int i ) const
-		{ return( i < 4 ? pr( a, 4 + i ) : pr( b, i - 4 )); }
+	f16 a;
+	__device__ __forceinline__ f2 f( int i ) const { return( splat( a[ i ])); }
+	__device__ __forceinline__ f2 fe( int i ) const { return( splat( a[ 4 + i ])); }
 };
 
 __device__ __forceinline__ TapsE load_taps_e( const float* p0 )
 {
 	const float* const p = sgpr_ptr( p0 );
 	TapsE t;
-	asm volatile( "s_load_dwordx16 %0, %2, 0x0\n\t"
-		"s_load_dwordx16 %1, %2, 0x40\n\t"
+	asm volatile( "s_load_dwordx16 %0, %1, 0x0\n\t"
 		AVIRHIP_WAITCNT_LGKM( 0 )
-		: "=&s"( t.a ), "=&s"( t.b ) : "s"( p ) : "memory" );
+		: "=&s"( t.a ) : "s"( p ) : "memory" );
 	return( t );
 }
 
+// packed f0..3 (the horizontal FIR)
+__device__ __forceinline__ f4 load_f4( const float* p0 )
+{
+	const float* const p = sgpr_ptr( p0 );
+	f4 t;
+	asm volatile( "s_load_dwordx4 %0, %1, 0x0\n\t" AVIRHIP_WAITCNT_LGKM( 0 )
+		: "=&s"( t ) : "s"( p ) : "memory" );
+	return( t );
+}
+
+// paired f0..3 (the horizontal FIR of the plain form)
 __device__ __forceinline__ f8 load_f8( const float* p0 )
 {
 	const float* const p = sgpr_ptr( p0 );
@@ -667,7 +714,7 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 	{
 		if( VT && U2_ON( 2 ))
 		{
-			const Taps H = load_taps( P.coef );
+			const TapsI H = load_taps_i( P.coef );
 			const lds_cf4 c0 = (lds_cf4) (unsigned long long) lo16( pkA );
 			const lds_f4 t0 = (lds_f4) (unsigned long long)
 				( t16 + (unsigned) (unsigned long long) (ldsptr) sT );
@@ -721,7 +768,7 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 		else
 		if( U2_ON( 2 ))
 		{
-			const Taps H = load_taps( P.coef );
+			const Taps H = load_taps( P.coef + U2_PAIRED );
 			const int tid = ( VT ? fresh_tid( wave ) : (int) threadIdx.x );
 			const int qq = tid & ( U2_TW / 2 - 1 );
 
@@ -825,12 +872,12 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 		// ---- V: one half-column per thread, statically unrolled marching.
 		// FAST: every row of this step is stored by every lane (interior of
 		// the chunk, full strip): no per-row conditions at all.
-		const Taps V = load_taps( P.coef + 64 );
+		const Taps V = load_taps( P.coef + U2_PAIRED + 64 );
 		// horizontal FIR taps (4 pairs), parked in VGPRs: the vertical taps
 		// already fill the SGPR file
 		f2 hv[ 4 ];
 		{
-			const f8 HF = load_f8( P.coef );
+			const f8 HF = load_f8( P.coef + U2_PAIRED );
 #pragma unroll
 			for( int t = 0; t < 4; t++ )
 			{
@@ -941,13 +988,12 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 
 	{
 		// H1 of the first tile (later tiles: woven into the vertical phase)
-		const f8 HF = load_f8( P.coef );
+		const f4 HF = load_f4( P.coef );
 		f2 hp[ 4 ];
 #pragma unroll
 		for( int t = 0; t < 4; t++ )
 		{
-			hp[ t ].x = HF[ t * 2 ];
-			hp[ t ].y = HF[ t * 2 + 1 ];
+			hp[ t ] = splat( HF[ t ]);
 		}
 
 #pragma unroll
@@ -1053,16 +1099,16 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 		{
 			constexpr int R0 = decltype( R0C )::value;
 			constexpr int MODE = decltype( MODEC )::value;
-			const TapsE V = load_taps_e( P.coef + 64 );
-			// the horizontal FIR taps stay in SGPRs too (16 + 4 pairs in all)
+			const TapsE V = load_taps_e( P.coef + 32 );
+			// the horizontal FIR taps stay in SGPRs too (16 + 4 taps in all,
+			// 10 pairs)
 			f2 hv[ 4 ];
 			{
-				const f8 HF = load_f8( P.coef );
+				const f4 HF = load_f4( P.coef );
 #pragma unroll
 				for( int t = 0; t < 4; t++ )
 				{
-					hv[ t ].x = HF[ t * 2 ];
-					hv[ t ].y = HF[ t * 2 + 1 ];
+					hv[ t ] = splat( HF[ t ]);
 				}
 			}
 
@@ -1197,6 +1243,10 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 				}
 
 				so += 2 * drow_b;
+				// (one running offset in one SGPR: the compiler otherwise keeps
+				// so + k * drow_b of every row of the ring period in SGPRs of
+				// their own -- 30 of them, spilled into VGPR lanes)
+				asm volatile( "" : "+s"( so ));
 
 				// ---- H1 of the next step, one iteration
 				// (unconditional: after the chunk's last step it works on
@@ -1411,12 +1461,17 @@ int up2_prepare( avirhip_plan* p )
 
 	if( match_axis( p -> h, D -> h ) && match_axis( p -> v, D -> v ))
 	{
-		float hc[ 128 ] = { 0 };
+		// the kernel's tap blocks, packed and paired (Up2Params::coef, Taps)
+		float hc[ U2_PAIRED + 128 ] = { 0 };
 		const Up2Axis* ax[ 2 ] = { &D -> h, &D -> v };
 
 		for( int a = 0; a < 2; a++ )
 		{
-			float* o = hc + a * 64;
+			float* o = hc + a * 32;
+			memcpy( o, ax[ a ] -> f, 4 * sizeof( float ));
+			memcpy( o + 4, ax[ a ] -> fe, 12 * sizeof( float ));
+			memcpy( o + 16, ax[ a ] -> fo, 12 * sizeof( float ));
+			o = hc + U2_PAIRED + a * 64;
 
 			for( int i = 0; i < 4; i++ )
 			{
