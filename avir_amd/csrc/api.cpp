@@ -733,8 +733,10 @@ static int run_generic( avirhip_plan* p, const float* src, long src_stride,
 static void band_src_rows( const avirhip_plan* p, int row0, int row1,
 	int* first, int* last );
 
+// `win`: a native source window (exec_any) -- `src` is then the virtual frame
+// base of the marching kernels, which are the only kernels such a call reaches
 static int exec_device( avirhip_plan* p, const void* src, void* dst,
-	int row0, int row1, hipStream_t st )
+	int row0, int row1, hipStream_t st, const SrcWindow win = SrcWindow{ 0, 0 })
 {
 	int rc;
 
@@ -894,7 +896,7 @@ static int exec_device( avirhip_plan* p, const void* src, void* dst,
 		if( lpath == 4 )
 		{
 			rc = lanc2_run( p, (const float*) src, (float*) dst, row0, row1,
-				st );
+				st, win );
 
 			if( rc != 1 )
 			{
@@ -1086,7 +1088,7 @@ static int exec_device( avirhip_plan* p, const void* src, void* dst,
 			if( iout4 != nullptr && uraw )
 			{
 				rc = up2_run( p, nullptr, 0, nullptr, row0, row1, st, iout4, src,
-					p -> src_stride );
+					p -> src_stride, win );
 
 				if( rc == 0 )
 				{
@@ -1102,7 +1104,8 @@ static int exec_device( avirhip_plan* p, const void* src, void* dst,
 
 			if( iout4 != nullptr )
 			{
-				rc = up2_run( p, fsrc, sstride, nullptr, row0, row1, st, iout4 );
+				rc = up2_run( p, fsrc, sstride, nullptr, row0, row1, st, iout4,
+					nullptr, 0, win );
 
 				if( rc == 0 )
 				{
@@ -1112,7 +1115,8 @@ static int exec_device( avirhip_plan* p, const void* src, void* dst,
 
 			if( rc == 1 )
 			{
-				rc = up2_run( p, fsrc, sstride, fdst, row0, row1, st );
+				rc = up2_run( p, fsrc, sstride, fdst, row0, row1, st, nullptr,
+					nullptr, 0, win );
 			}
 		}
 		else
@@ -1304,7 +1308,7 @@ static int band_last_src_row( const avirhip_plan* p, int row0, int row1 )
 // call costs the longer direction instead of the sum (cfg3: 531 MB down,
 // 133 MB up). Returns 1 when the call should take the serial path.
 static int exec_device( avirhip_plan* p, const void* src, void* dst,
-	int row0, int row1, hipStream_t st );
+	int row0, int row1, hipStream_t st, const SrcWindow win );
 
 static int exec_host_pipelined( avirhip_plan* p, const void* src, void* dst,
 	size_t src_bytes, size_t dst_bytes, size_t row_bytes, hipStream_t st )
@@ -1519,7 +1523,8 @@ static int exec_host_pipelined( avirhip_plan* p, const void* src, void* dst,
 		}
 
 		rc = exec_device( p, dsrc, (char*) p -> stage_dst +
-			(size_t) cut[ b ] * row_bytes, cut[ b ], cut[ b + 1 ], st );
+			(size_t) cut[ b ] * row_bytes, cut[ b ], cut[ b + 1 ], st,
+			SrcWindow{ 0, 0 });
 
 		if( rc != AVIRHIP_OK )
 		{
@@ -1649,10 +1654,18 @@ static int exec_any( avirhip_plan* p, const void* src, int src_mem, void* dst,
 	const size_t dst_bytes = ( row1 > row0 ?
 		(size_t) ( row1 - row0 - 1 ) * row_bytes + (size_t) p -> new_w *
 		p -> io_ch * dtype_size( p -> out_type ) : 0 );
-	const bool overlap = ( !windowed && src_mem == AVIRHIP_MEM_DEVICE &&
+	// (device buffers that share bytes: [src, src + win_bytes) is what `src`
+	// addresses, a window's rows included)
+	const bool shared = ( src_mem == AVIRHIP_MEM_DEVICE &&
 		dst_mem == AVIRHIP_MEM_DEVICE &&
 		(const char*) src < (const char*) dst + dst_bytes &&
-		(const char*) dst < (const char*) src + src_bytes );
+		(const char*) dst < (const char*) src + win_bytes );
+	const bool overlap = ( !windowed && shared );
+	// a window that overlaps its destination band: a staged window is copied
+	// before anything is stored; a native one would be read where it lies while
+	// the band is written -- it is copied aside first, like a host window
+	const bool win_aside = ( windowed && ( shared ||
+		src_mem == AVIRHIP_MEM_HOST ));
 
 	const int xpath = ( p -> path != 0 ? p -> path : p -> auto_path );
 	// (CLancIR is not thread-safe in the reference either, lancir.h:319-349:
@@ -1822,11 +1835,11 @@ static int exec_any( avirhip_plan* p, const void* src, int src_mem, void* dst,
 	const bool dst_direct = ( dst_mem == AVIRHIP_MEM_DEVICE );
 	bool win_native = false;
 
-	if( windowed && !overlap && getenv( "AVIRHIP_NO_NATIVE_WINDOW" ) == nullptr )
+	if( windowed && getenv( "AVIRHIP_NO_NATIVE_WINDOW" ) == nullptr )
 	{
 		// (alignment of the pointers the kernel will see: the staging buffers
 		// are 256-byte aligned, win_off is a multiple of the row pitch)
-		const void* const vsrc = (const char*) ( src_mem == AVIRHIP_MEM_DEVICE ?
+		const void* const vsrc = (const char*) ( !win_aside ?
 			src : (const void*) (uintptr_t) 256 ) - ( win_off & 255 );
 		const void* const vdst = ( dst_direct ? dst : (void*) (uintptr_t) 256 );
 
@@ -1835,14 +1848,11 @@ static int exec_any( avirhip_plan* p, const void* src, int src_mem, void* dst,
 			up2_takes_window( p, vsrc, vdst )));
 	}
 
-	// (the window fields are the plan's for this call only: the lock is held)
-	struct WindowScope
-	{
-		avirhip_plan* p;
-		~WindowScope() { p -> win_first = 0; p -> win_rows = 0; }
-	} winscope = { p };
+	// (the kernels' row clamp: an argument of this call, never the plan's)
+	SrcWindow kwin = { 0, 0 };
 
-	if( src_mem == AVIRHIP_MEM_HOST || ( windowed && !win_native ))
+	if( src_mem == AVIRHIP_MEM_HOST || ( windowed && ( !win_native ||
+		win_aside )))
 	{
 		const size_t need = ( win_native ? win_bytes : src_bytes );
 
@@ -1860,16 +1870,17 @@ static int exec_any( avirhip_plan* p, const void* src, int src_mem, void* dst,
 
 	if( windowed && win_native )
 	{
-		if( src_mem == AVIRHIP_MEM_HOST )
+		if( win_aside )
 		{
 			AVIRHIP_HIPCHECK( hipMemcpyAsync( p -> stage_src, src, win_bytes,
-				hipMemcpyHostToDevice, st ));
+				( src_mem == AVIRHIP_MEM_HOST ? hipMemcpyHostToDevice :
+				hipMemcpyDeviceToDevice ), st ));
 		}
 
 		// (pointer arithmetic only: nothing below row win_first is ever read)
 		dsrc = (const void*) ( (uintptr_t) dsrc - win_off );
-		p -> win_first = win_first;
-		p -> win_rows = win_rows;
+		kwin.first = win_first;
+		kwin.rows = win_rows;
 	}
 	else
 	if( windowed )
@@ -1946,7 +1957,7 @@ static int exec_any( avirhip_plan* p, const void* src, int src_mem, void* dst,
 			hipMemcpyHostToDevice, st ));
 	}
 
-	rc = exec_device( p, dsrc, ddst, row0, row1, st );
+	rc = exec_device( p, dsrc, ddst, row0, row1, st, kwin );
 	if( rc != 0 ) return( rc );
 
 	if( dst_mem == AVIRHIP_MEM_HOST )
@@ -2020,7 +2031,6 @@ static avirhip_plan* new_plan()
 	p -> packed = nullptr; p -> resbuf = nullptr; p -> lres = nullptr;
 	p -> stage_src = nullptr; p -> stage_dst = nullptr;
 	p -> stage_src_bytes = 0; p -> stage_dst_bytes = 0;
-	p -> win_first = 0; p -> win_rows = 0;
 	p -> shard_band = nullptr; p -> shard_band_bytes = 0; p -> shard_ldev = -1;
 	p -> last_done = nullptr; p -> last_stream = nullptr; p -> last_used = false;
 	p -> last_recorded = false;

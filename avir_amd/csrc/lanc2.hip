@@ -563,7 +563,7 @@ bool lanc2_takes_window( const avirhip_plan* p, const void* src, const void* dst
 // horizontal phase runs the owner's output stage and stores into its image;
 // dst is not used then. Sets p -> lfuse.done.
 int lanc2_run( avirhip_plan* p, const float* src, float* dst, int row0,
-	int row1, hipStream_t st )
+	int row1, hipStream_t st, SrcWindow win )
 {
 	const Lanc2Data* D = (const Lanc2Data*) p -> lanc2;
 	const int io = ( !p -> lfuse.on ? 0 :
@@ -619,8 +619,8 @@ int lanc2_run( avirhip_plan* p, const float* src, float* dst, int row0,
 	Lanc2Params P;
 	P.src = src; P.src_ss = p -> src_stride; P.sw = p -> src_w;
 	P.sh = p -> src_h;
-	P.rmin = ( p -> win_rows > 0 ? p -> win_first : 0 );
-	P.rmax = ( p -> win_rows > 0 ? p -> win_first + p -> win_rows : p -> src_h ) - 1;
+	P.rmin = ( win.rows > 0 ? win.first : 0 );
+	P.rmax = ( win.rows > 0 ? win.first + win.rows : p -> src_h ) - 1;
 	P.dst = dst; P.dst_ss = (long) p -> new_w * 4; P.dst_row0 = row0;
 	P.nw = p -> new_w; P.nh = p -> new_h;
 	P.srow_lo = row0; P.srow_hi = row1;

@@ -212,16 +212,22 @@ struct avirhip_plan
 	void* stage_src; // host-pointer staging
 	void* stage_dst;
 	size_t stage_src_bytes, stage_dst_bytes;
-	// avirhip_resize_window on the marching kernels (k_up2, k_lanc2): the source
-	// pointer handed to them is a VIRTUAL frame base -- window - win_first rows
-	// -- and only rows [win_first, win_first + win_rows) exist behind it: the
-	// kernels clamp their row indices to that range instead of [0, src_h)
-	// (set by exec_any under the plan's lock for the duration of one call;
-	// win_rows == 0: the whole frame)
-	int win_first, win_rows;
 };
 
+
 namespace avirhip {
+
+// avirhip_resize_window on the marching kernels (k_up2, k_lanc2): the source
+// pointer handed to them is a VIRTUAL frame base -- window - first rows -- and
+// only rows [first, first + rows) exist behind it: the kernels clamp their row
+// indices to that range instead of [0, src_h). An argument of the call, from
+// exec_any down to up2_run / lanc2_run, never state of the plan: whole-frame
+// calls of the same plan run beside a window call without the plan's lock.
+// (rows == 0: the whole frame)
+struct SrcWindow
+{
+	int first, rows;
+};
 
 void set_error( const char* fmt, ... );
 void clear_error();
@@ -402,7 +408,8 @@ int up2_prepare( avirhip_plan* p );
 void up2_release( avirhip_plan* p );
 int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 	int row0, int row1, hipStream_t st, void* iout = nullptr,
-	const void* raw = nullptr, long raw_stride = 0 );
+	const void* raw = nullptr, long raw_stride = 0,
+	SrcWindow win = SrcWindow{ 0, 0 });
 bool up2_stores_io( const avirhip_plan* p );
 // whether up2_run / lanc2_run take this float RGBA call for certain (no refusal,
 // no fall-back to kernels that know nothing of a source window)
@@ -413,7 +420,7 @@ bool lanc2_takes_window( const avirhip_plan* p, const void* src, const void* dst
 int lanc2_prepare( avirhip_plan* p );
 void lanc2_release( avirhip_plan* p );
 int lanc2_run( avirhip_plan* p, const float* src, float* dst, int row0,
-	int row1, hipStream_t st );
+	int row1, hipStream_t st, SrcWindow win = SrcWindow{ 0, 0 });
 bool lanc2_takes_raw( const avirhip_plan* q, const void* raw, int type, int ch,
 	long stride );
 

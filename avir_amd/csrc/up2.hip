@@ -1559,7 +1559,7 @@ bool up2_takes_window( const avirhip_plan* p, const void* src, const void* dst )
 // if this call cannot take it (the caller then packs and calls again).
 int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 	int row0, int row1, hipStream_t st, void* iout, const void* raw,
-	long raw_stride )
+	long raw_stride, SrcWindow win )
 {
 	const Up2Data* D = (const Up2Data*) p -> up2;
 	static const bool novt = ( getenv( "AVIRHIP_UP2_NOVT" ) != nullptr );
@@ -1603,7 +1603,7 @@ int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 		const long sb = raw_stride * esz;
 
 		if(( io != 4 && io != 5 ) || ( p -> io_ch != 3 && p -> io_ch != 4 ) ||
-			p -> win_rows > 0 || ( (uintptr_t) raw & ( esz - 1 )) ||
+			win.rows > 0 || ( (uintptr_t) raw & ( esz - 1 )) ||
 			( esz == 2 && p -> io_ch == 4 && (( (uintptr_t) raw | sb ) & 3 )) ||
 			sb >= ( 1L << 22 ) || getenv( "AVIRHIP_UP2_NO_RAW" ) != nullptr )
 		{
@@ -1637,8 +1637,8 @@ int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 
 	Up2Params P;
 	P.src = src; P.src_ss = src_stride; P.sw = p -> src_w; P.sh = p -> src_h;
-	P.rmin = ( p -> win_rows > 0 ? p -> win_first : 0 );
-	P.rmax = ( p -> win_rows > 0 ? p -> win_first + p -> win_rows : p -> src_h ) - 1;
+	P.rmin = ( win.rows > 0 ? win.first : 0 );
+	P.rmax = ( win.rows > 0 ? win.first + win.rows : p -> src_h ) - 1;
 	P.dst = dst; P.dst_ss = (long) p -> new_w * 4; P.dst_row0 = row0;
 	P.nw = p -> new_w; P.nh = p -> new_h;
 	P.srow_lo = row0; P.srow_hi = row1;

@@ -324,7 +324,16 @@ int avirhip_band_source_rows(const avirhip_plan* plan, int row0, int row1,
  * reaches a result is the frame's own edge replication), a HOST window is
  * uploaded into a window-sized staging buffer. Other plans copy the window to
  * its place in a frame-sized staging buffer of the plan (their kernels index
- * the frame; what they load outside the window never reaches a result). */
+ * the frame; what they load outside the window never reaches a result:
+ * tests/test_gpu_window.py runs every kernel family from windows whose
+ * surroundings -- the rest of that buffer included -- are NaNs / complemented
+ * pixels, against the reference's bits).
+ * A DEVICE window may share bytes with `dst_band`: the window is then copied
+ * aside before anything is stored (into the window-sized staging buffer on the
+ * marching kernels), and the band is the same as from a disjoint window.
+ * The window is an argument of the call, not state of the plan: window calls,
+ * whole-frame calls and band calls of one plan may run on different threads at
+ * the same time (avirhip_plan_create). */
 int avirhip_resize_window(avirhip_plan* plan, const void* src_rows,
 	int src_mem, int first_row, int n_rows, void* dst_band, int dst_mem,
 	int row0, int row1, void* stream);
