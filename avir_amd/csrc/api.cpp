@@ -161,6 +161,35 @@ static int dev_alloc( avirhip_plan* p, size_t bytes, void** out )
 	return( AVIRHIP_OK );
 }
 
+// a scratch buffer of at least `need` bytes (a larger one replaces it)
+static int grow( avirhip_plan* p, void** buf, size_t* have, size_t need )
+{
+	if( *have < need )
+	{
+		void* q;
+		const int rc = dev_alloc( p, need, &q );
+		if( rc != 0 ) return( rc );
+		*buf = q;
+		*have = need;
+	}
+
+	return( AVIRHIP_OK );
+}
+
+// a scratch buffer of `n` floats, allocated when it is first needed
+static int need_floats( avirhip_plan* p, float** buf, size_t n )
+{
+	if( *buf == nullptr )
+	{
+		void* q;
+		const int rc = dev_alloc( p, n * sizeof( float ), &q );
+		if( rc != 0 ) return( rc );
+		*buf = (float*) q;
+	}
+
+	return( AVIRHIP_OK );
+}
+
 // ---- lowering of one AVIR axis (see plan.h for the view semantics) ----
 
 static int lower_axis( const avirhip_axis& ax, int src_len, int dst_len,
@@ -569,48 +598,28 @@ void need_range( const LOp& op, int a, int b, int& ia, int& ib )
 
 static int ensure_scratch( avirhip_plan* p )
 {
+	int rc;
+
 	if( p -> is_lancir )
 	{
-		if( p -> resbuf == nullptr )
-		{
-			void* q;
-			int rc = dev_alloc( p, (size_t) p -> new_h * p -> src_w *
-				p -> ch * sizeof( float ), &q );
-			if( rc != 0 ) return( rc );
-			p -> resbuf = (float*) q;
-		}
+		if(( rc = need_floats( p, &p -> resbuf, (size_t) p -> new_h *
+			p -> src_w * p -> ch )) != 0 ) return( rc );
 
-		if( p -> lres == nullptr &&
-			!( p -> out_type == AVIRHIP_F32 && p -> l_unity ))
-		{
-			void* q;
-			int rc = dev_alloc( p, (size_t) p -> new_h * p -> new_w *
-				p -> ch * sizeof( float ), &q );
-			if( rc != 0 ) return( rc );
-			p -> lres = (float*) q;
-		}
+		if( !( p -> out_type == AVIRHIP_F32 && p -> l_unity ) &&
+			( rc = need_floats( p, &p -> lres, (size_t) p -> new_h *
+			p -> new_w * p -> ch )) != 0 ) return( rc );
 
 		return( AVIRHIP_OK );
 	}
 
-	int rc;
-	void* q;
-
 	if(( p -> in_type != AVIRHIP_F32 || p -> gamma || p -> ch != p -> io_ch ) &&
-		p -> packed == nullptr )
-	{
-		if(( rc = dev_alloc( p, (size_t) p -> src_w * p -> src_h * p -> ch *
-			sizeof( float ), &q )) != 0 ) return( rc );
-		p -> packed = (float*) q;
-	}
+		( rc = need_floats( p, &p -> packed, (size_t) p -> src_w * p -> src_h *
+		p -> ch )) != 0 ) return( rc );
 
 	if(( p -> out_type != AVIRHIP_F32 || p -> ch != p -> io_ch ||
-		( p -> fp4 && p -> gamma )) && p -> resbuf == nullptr )
-	{
-		if(( rc = dev_alloc( p, (size_t) p -> new_w * p -> new_h * p -> ch *
-			sizeof( float ), &q )) != 0 ) return( rc );
-		p -> resbuf = (float*) q;
-	}
+		( p -> fp4 && p -> gamma )) &&
+		( rc = need_floats( p, &p -> resbuf, (size_t) p -> new_w * p -> new_h *
+		p -> ch )) != 0 ) return( rc );
 
 	return( AVIRHIP_OK );
 }
@@ -730,505 +739,6 @@ static int run_generic( avirhip_plan* p, const float* src, long src_stride,
 	return( AVIRHIP_OK );
 }
 
-static void band_src_rows( const avirhip_plan* p, int row0, int row1,
-	int* first, int* last );
-
-// `win`: a native source window (exec_any) -- `src` is then the virtual frame
-// base of the marching kernels, which are the only kernels such a call reaches
-static int exec_device( avirhip_plan* p, const void* src, void* dst,
-	int row0, int row1, hipStream_t st, const SrcWindow win = SrcWindow{ 0, 0 })
-{
-	int rc;
-
-	if( p -> f64 )
-	{
-		return( exec_f64( p, src, dst, row0, row1, st ));
-	}
-
-	// LANCIR: the exact-2x kernel needs no scratch; the generic kernels'
-	// intermediate is only allocated when they actually run
-	if( !p -> is_lancir && ( rc = ensure_scratch( p )) != 0 ) return( rc );
-
-	if( p -> is_lancir && p -> inner != nullptr && p -> path != 1 )
-	{
-		avirhip_plan* const q = p -> inner;
-		const LancirAxisDev& V = p -> lv;
-		void* m;
-
-		if( row1 <= row0 )
-		{
-			return( AVIRHIP_OK );
-		}
-
-		// The float RGBA copy of the source and the float result are only
-		// allocated when a pass needs them: with the raw loader and the fused
-		// output stage (the automatic path of uint8 / uint16 images) neither
-		// is touched -- 16 bytes per source and per destination pixel, per
-		// plan, spare and replica, that also count against the plan cache.
-		auto need_lres = [&]() -> int
-		{
-			if( p -> lres == nullptr )
-			{
-				const int r = dev_alloc( p, (size_t) p -> new_w * p -> new_h * 4 *
-					sizeof( float ), &m );
-
-				if( r != 0 ) return( r );
-				p -> lres = (float*) m;
-			}
-
-			return( AVIRHIP_OK );
-		};
-
-		// the source rows this band's vertical windows read
-		const int sa = std::max( 0, std::min( V.h_start[ row0 ],
-			p -> src_h - 1 ));
-		const int sb = std::max( 0, std::min( V.h_start[ row1 - 1 ] +
-			V.kernel_len - 1, p -> src_h - 1 ));
-		const size_t es = dtype_size( p -> in_type );
-		// (double and uint32 elements, lancir.h:373-377: the pack pass and the
-		// output stage convert them; the fast kernels' own loaders and fused
-		// stores know uint8, uint16 and float)
-		const bool in_fast = ( p -> in_type <= AVIRHIP_F32 );
-		const bool out_fast = ( p -> out_type <= AVIRHIP_F32 );
-
-		q -> path = p -> path;
-
-		// the inner plan's first pass reads this image itself where it can;
-		// otherwise the pack pass makes its float RGBA copy
-		q -> lraw.on = ( getenv( "AVIRHIP_NO_FUSED_OUT" ) == nullptr && in_fast &&
-			( gpass_lancir_takes_raw( q, src, p -> in_type, p -> io_ch,
-			p -> src_stride ) || ( lanc2_takes_raw( q, src,
-			p -> in_type, p -> io_ch, p -> src_stride ) &&
-			// (RGBA: its integer stage stores a lane's two elements at once)
-			( p -> io_ch == 3 || ( p -> new_stride & 1 ) == 0 ) &&
-			( p -> out_type != AVIRHIP_U8 || p -> io_ch == 3 ||
-			( (uintptr_t) dst & 1 ) == 0 ) &&
-			( p -> out_type != AVIRHIP_U16 ||
-			( (uintptr_t) dst & ( p -> io_ch == 3 ? 1 : 3 )) == 0 ) &&
-			( p -> out_type != AVIRHIP_F32 || ( (uintptr_t) dst & 3 ) == 0 ))));
-
-		q -> lraw.ptr = src; q -> lraw.type = p -> in_type;
-		q -> lraw.ch = p -> io_ch; q -> lraw.stride = p -> src_stride;
-
-		auto do_pack = [&]() -> int
-		{
-			if( p -> packed == nullptr )
-			{
-				const int r = dev_alloc( p, (size_t) p -> src_w * p -> src_h * 4 *
-					sizeof( float ), &m );
-
-				if( r != 0 ) return( r );
-				p -> packed = (float*) m;
-			}
-
-			return( launch_pack( (const char*) src +
-				(size_t) sa * p -> src_stride * es, p -> in_type, p -> packed +
-				(size_t) sa * p -> src_w * 4, p -> src_w, sb - sa + 1,
-				p -> io_ch, 4, p -> src_stride, st ));
-		};
-
-		if( !q -> lraw.on && ( rc = do_pack() ) != 0 ) return( rc );
-
-		q -> lfuse.on = ( getenv( "AVIRHIP_NO_FUSED_OUT" ) == nullptr &&
-			out_fast );
-		q -> lfuse.done = 0;
-		q -> lfuse.type = p -> out_type; q -> lfuse.ch = p -> io_ch;
-		q -> lfuse.unity = p -> l_unity; q -> lfuse.out_mul = p -> l_out_mul;
-		q -> lfuse.clampv = p -> l_clamp;
-		q -> lfuse.dst = dst; q -> lfuse.stride = p -> new_stride;
-
-		// (a null result buffer: only the fused store may run; a pass that
-		// would write the float result returns AVIRHIP_NEED_DST first)
-		if( !q -> lfuse.on && ( rc = need_lres() ) != 0 ) return( rc );
-
-		rc = exec_device( q, p -> packed, p -> lres, row0, row1, st );
-
-		// (at most one round of each: the kernel that was to read the owner's
-		// image refused the call -> float copy; a pass would have written the
-		// float result -> result buffer)
-		for( int round = 0; round < 2 && ( rc == AVIRHIP_NEED_SRC ||
-			rc == AVIRHIP_NEED_DST ); round++ )
-		{
-			if( rc == AVIRHIP_NEED_SRC )
-			{
-				q -> lraw.on = 0;
-				if(( rc = do_pack() ) != 0 ) break;
-			}
-			else
-			if(( rc = need_lres() ) != 0 ) break;
-
-			q -> lfuse.done = 0;
-			rc = exec_device( q, p -> packed, p -> lres, row0, row1, st );
-		}
-
-		q -> lfuse.on = 0;
-		q -> lraw.on = 0;
-
-		if( rc == AVIRHIP_NEED_SRC || rc == AVIRHIP_NEED_DST )
-		{
-			set_error( "LANCIR: the inner plan kept asking for buffers (%d)", rc );
-			return( AVIRHIP_EINTERNAL );
-		}
-
-		if( rc != 0 || q -> lfuse.done )
-		{
-			return( rc );
-		}
-
-		if( p -> io_ch == 4 )
-		{
-			return( launch_lancir_out( p, p -> lres, (long) p -> new_w * 4, dst,
-				row1 - row0, st ));
-		}
-
-		return( launch_lancir_out_pad( p, p -> lres, dst, row1 - row0, st ));
-	}
-
-	if( p -> is_lancir )
-	{
-		const int lpath = ( p -> path != 0 ? p -> path : p -> auto_path );
-
-		if( lpath == 4 && dst == nullptr && !p -> lfuse.on )
-		{
-			return( AVIRHIP_NEED_DST );
-		}
-
-		if( lpath == 4 )
-		{
-			rc = lanc2_run( p, (const float*) src, (float*) dst, row0, row1,
-				st, win );
-
-			if( rc != 1 )
-			{
-				return( rc );
-			}
-
-			if( p -> lraw.on )
-			{
-				// (the kernels below would read the float copy the owner skipped)
-				return( AVIRHIP_NEED_SRC );
-			}
-
-			if( p -> path != 0 )
-			{
-				set_error( "path 4 cannot run this call (unaligned buffers?)" );
-				return( AVIRHIP_EUNSUPPORTED );
-			}
-		}
-
-		if( lpath == 5 || ( lpath == 4 && p -> path == 0 && gpass_ok( p )))
-		{
-			// general-ratio pass kernels (vertical pass first)
-			rc = gpass_run( p, (const float*) src, p -> src_stride,
-				(float*) dst, row0, row1, st );
-
-			if( rc != 1 )
-			{
-				return( rc );
-			}
-
-			if( p -> path != 0 )
-			{
-				set_error( "path 5 cannot run this call (unaligned buffers?)" );
-				return( AVIRHIP_EUNSUPPORTED );
-			}
-		}
-
-		if( dst == nullptr )
-		{
-			return( AVIRHIP_NEED_DST );
-		}
-
-		if(( rc = ensure_scratch( p )) != 0 ) return( rc );
-
-		return( launch_lancir_generic( p, src, dst, p -> resbuf, row0, row1,
-			st ));
-	}
-
-	const float* fsrc = (const float*) src;
-	long sstride = p -> src_stride;
-
-	const int path = ( p -> path != 0 ? p -> path : p -> auto_path );
-
-	// integer sources on the tiled paths: the tile loader converts and pads
-	// them itself, the float copy of the source (pack pass) is skipped
-	const bool raw = ( !p -> gamma && ( path == 2 || path == 3 ) &&
-		( p -> in_type == AVIRHIP_U8 || p -> in_type == AVIRHIP_U16 ) &&
-		p -> ch == 4 && fused_takes_raw( p, path ));
-
-	bool packed_done = false;
-	auto do_pack = [&]() -> int
-	{
-		if( packed_done )
-		{
-			return( AVIRHIP_OK );
-		}
-
-		packed_done = true;
-
-		// a band converts the source rows its windows read, nothing else (the
-		// pipelined host-pointer call is 16 bands: 16 whole-frame packs otherwise)
-		int pa, pb;
-		band_src_rows( p, row0, row1, &pa, &pb );
-
-		if( pb < pa )
-		{
-			return( AVIRHIP_OK );
-		}
-
-		const char* const ps = (const char*) src + (size_t) pa *
-			p -> src_stride * dtype_size( p -> in_type );
-		float* const pd = p -> packed + (size_t) pa * p -> src_w * p -> ch;
-
-		if( p -> gamma )
-		{
-			return( launch_pack_gamma( ps, p -> in_type, pd, p -> src_w,
-				pb - pa + 1, p -> io_ch, p -> ch, p -> src_stride,
-				p -> alpha_index, p -> d_srgb_tbl, st ));
-		}
-
-		return( launch_pack( ps, p -> in_type, pd, p -> src_w, pb - pa + 1,
-			p -> io_ch, p -> ch, p -> src_stride, st ));
-	};
-
-	const bool need_pack = ( p -> gamma || p -> in_type != AVIRHIP_F32 ||
-		p -> ch != p -> io_ch );
-
-	// the streaming pass kernel reads integer / narrower sources as they are
-	const bool graw = ( need_pack && !p -> gamma && path == 5 &&
-		( p -> in_type == AVIRHIP_U8 || p -> in_type == AVIRHIP_U16 ||
-		p -> in_type == AVIRHIP_F32 ) && p -> ch == 4 && gpass_takes_raw( p ));
-
-	// the exact-2x marching kernel reads RGB / RGBA uint8 / uint16 images as
-	// they lie when it also stores the caller's integer pixels (it may still
-	// refuse the call -- alignment, a source window: the pack pass runs then)
-	const bool uraw = ( need_pack && !p -> gamma && path == 4 && !p -> is_lancir &&
-		( p -> in_type == AVIRHIP_U8 || p -> in_type == AVIRHIP_U16 ) &&
-		p -> ch == 4 && ( p -> io_ch == 3 || p -> io_ch == 4 ) &&
-		( p -> out_type == AVIRHIP_U8 || p -> out_type == AVIRHIP_U16 ) &&
-		p -> dither == AVIRHIP_DITHER_DEF && up2_stores_io( p ) &&
-		getenv( "AVIRHIP_NO_FUSED_OUT" ) == nullptr );
-
-	if( need_pack && !raw && !graw && !uraw )
-	{
-		if(( rc = do_pack()) != 0 ) return( rc );
-	}
-
-	if( need_pack )
-	{
-		fsrc = p -> packed;
-		sstride = (long) p -> src_w * p -> ch;
-	}
-
-	// float output is the vertical pass' in-place result (avir.h:4956-4979):
-	// with gamma it stays linear, only the other output types are
-	// de-linearised in the epilogue
-	// (fpclass_float4 has no in-place output: its float results pass through
-	// the output stage like every other type, which matters with gamma)
-	const bool direct = ( p -> out_type == AVIRHIP_F32 &&
-		p -> ch == p -> io_ch && !( p -> fp4 && p -> gamma ));
-
-	float* fdst = ( direct ? (float*) dst : p -> resbuf );
-
-	rc = 1;
-
-	if( path >= 2 && path <= 5 )
-	{
-		if( path == 5 )
-		{
-			// integer output without gamma / error diffusion: the last pass
-			// converts and stores into the caller's image itself
-			void* iout = ( !direct && !p -> gamma &&
-				(( p -> dither == AVIRHIP_DITHER_DEF &&
-				( p -> out_type == AVIRHIP_U8 || p -> out_type == AVIRHIP_U16 )) ||
-				p -> out_type == AVIRHIP_F32 ) &&
-				getenv( "AVIRHIP_NO_FUSED_OUT" ) == nullptr ? dst : nullptr );
-
-			if( !graw && need_pack && ( rc = do_pack()) != 0 ) return( rc );
-
-			for( int pass = 0; pass < 2; pass++ )
-			{
-				if( graw )
-				{
-					rc = gpass_run( p, nullptr, 0, fdst, row0, row1, st, src,
-						p -> in_type, p -> io_ch, p -> src_stride, iout );
-				}
-				else
-				{
-					rc = gpass_run( p, fsrc, sstride, fdst, row0, row1, st,
-						nullptr, 0, 0, 0, iout );
-				}
-
-				if( rc == 0 && iout != nullptr )
-				{
-					return( AVIRHIP_OK ); // (no epilogue)
-				}
-
-				if( rc != 1 || iout == nullptr )
-				{
-					break;
-				}
-
-				iout = nullptr; // this plan's last pass cannot: float result
-			}
-		}
-		else
-		if( path == 4 )
-		{
-			// integer / narrow output: the marching kernel's vertical phase
-			// converts and stores into the caller's image itself
-			void* iout4 = ( !direct && !p -> gamma &&
-				(( p -> dither == AVIRHIP_DITHER_DEF &&
-				( p -> out_type == AVIRHIP_U8 || p -> out_type == AVIRHIP_U16 )) ||
-				p -> out_type == AVIRHIP_F32 ) &&
-				getenv( "AVIRHIP_NO_FUSED_OUT" ) == nullptr ? dst : nullptr );
-
-			rc = 1;
-
-			if( iout4 != nullptr && uraw )
-			{
-				rc = up2_run( p, nullptr, 0, nullptr, row0, row1, st, iout4, src,
-					p -> src_stride, win );
-
-				if( rc == 0 )
-				{
-					return( AVIRHIP_OK ); // (no pack pass, no epilogue)
-				}
-
-				if( rc != 1 ) return( rc );
-			}
-
-			if( uraw && ( rc = do_pack()) != 0 ) return( rc );
-
-			rc = 1;
-
-			if( iout4 != nullptr )
-			{
-				rc = up2_run( p, fsrc, sstride, nullptr, row0, row1, st, iout4,
-					nullptr, 0, win );
-
-				if( rc == 0 )
-				{
-					return( AVIRHIP_OK ); // (no epilogue)
-				}
-			}
-
-			if( rc == 1 )
-			{
-				rc = up2_run( p, fsrc, sstride, fdst, row0, row1, st, nullptr,
-					nullptr, 0, win );
-			}
-		}
-		else
-		{
-			// integer / narrow output through the whole-ratio vertical kernel:
-			// it converts and stores into the caller's image itself
-			void* iout2 = ( !direct && !p -> gamma &&
-				(( p -> dither == AVIRHIP_DITHER_DEF &&
-				( p -> out_type == AVIRHIP_U8 || p -> out_type == AVIRHIP_U16 )) ||
-				p -> out_type == AVIRHIP_F32 ) &&
-				!( p -> out_type == AVIRHIP_U8 && p -> io_ch == 4 &&
-				( (uintptr_t) dst & 3 ) != 0 ) &&
-				fused_stores_int( p, path ) &&
-				getenv( "AVIRHIP_NO_FUSED_OUT" ) == nullptr ? dst : nullptr );
-
-			if( raw )
-			{
-				rc = fused_run( p, path, src, p -> in_type, p -> io_ch,
-					p -> src_stride, fdst, row0, row1, st, iout2 );
-			}
-			else
-			{
-				rc = fused_run( p, path, fsrc, AVIRHIP_F32, 4, sstride, fdst,
-					row0, row1, st, iout2 );
-			}
-
-			if( rc == 0 && iout2 != nullptr )
-			{
-				return( AVIRHIP_OK ); // (no epilogue)
-			}
-		}
-
-		if( rc == 1 && p -> path != 0 )
-		{
-			set_error( "path %d cannot run this call (unaligned buffers?)",
-				path );
-			return( AVIRHIP_EUNSUPPORTED );
-		}
-	}
-
-	if( rc == 1 && need_pack )
-	{
-		if(( rc = do_pack()) != 0 ) return( rc );
-		rc = 1;
-	}
-
-	if( rc == 1 )
-	{
-		rc = run_generic( p, fsrc, sstride, fdst, row0, row1, st );
-	}
-
-	if( rc != 0 ) return( rc );
-
-	if( !direct && p -> dither == AVIRHIP_DITHER_ERRD )
-	{
-		// recursive ditherer: whole frames only (exec_any refuses bands)
-		if( p -> errd_line == nullptr )
-		{
-			void* q;
-			// one row of diffusion values per pass of 448 rows (generic.hip:
-			// k_errd_mp; the single-workgroup kernels use two), then the
-			// passes' progress flags
-			const size_t np = (size_t) ( p -> new_h + 447 ) / 448 + 2;
-
-			if(( rc = dev_alloc( p, np * p -> new_w * 4 * sizeof( float ) +
-				np * sizeof( unsigned ) + 64, &q )) != 0 ) return( rc );
-			p -> errd_line = (float*) q;
-		}
-
-		rc = launch_errd( fdst, dst, p -> out_type, p -> new_w, p -> new_h,
-			p -> io_ch, p -> ch, p -> tr_mul, p -> pk_out, p -> gamma,
-			p -> alpha_index, p -> errd_line, st );
-	}
-	else
-	if( !direct )
-	{
-		rc = launch_epilogue( fdst, dst, p -> out_type,
-			(long) ( row1 - row0 ) * p -> new_w * p -> io_ch, p -> tr_mul,
-			p -> pk_out, ( p -> gamma && ( p -> out_type != AVIRHIP_F32 ||
-			p -> fp4 )), p -> io_ch, p -> ch, p -> alpha_index, st,
-			p -> d_gthr, ( p -> dither == AVIRHIP_DITHER_DEF_RNE ));
-	}
-
-	return( rc );
-}
-
-} // namespace avirhip
-
-// AVIRHIP_MEM_AUTO: device memory if the HIP runtime knows the pointer as such.
-extern "C" int avirhip_resolve_mem( const void* ptr, int mem )
-{
-	if( mem != AVIRHIP_MEM_AUTO )
-	{
-		return( mem );
-	}
-
-	hipPointerAttribute_t at;
-
-	if( ptr != nullptr && hipPointerGetAttributes( &at, ptr ) == hipSuccess &&
-		( at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged ))
-	{
-		return( AVIRHIP_MEM_DEVICE );
-	}
-
-	(void) hipGetLastError(); // unregistered host memory reports an error
-	return( AVIRHIP_MEM_HOST );
-}
-
-namespace avirhip {
-
-static int clone_plan( const avirhip_plan* s, int device, avirhip_plan** out );
-
 // The source rows [*first, *last] (inclusive) the output rows [row0, row1)
 // read: the vertical axis' op chain walked backwards (AVIR), the vertical
 // filter positions (LANCIR). Rows outside the range are never touched by a band
@@ -1300,6 +810,512 @@ static int band_last_src_row( const avirhip_plan* p, int row0, int row1 )
 	return( b );
 }
 
+// The switch for A/B timing and for tests of the unfused stages: with it, no
+// kernel reads the caller's image as it lies and none stores the caller's
+// pixels itself -- pack pass and output stage always run. Read once per process.
+static bool fused_io()
+{
+	static const bool on = ( getenv( "AVIRHIP_NO_FUSED_OUT" ) == nullptr );
+	return( on );
+}
+
+// ---- LANCIR ----
+
+// A LANCIR plan's own kernels, fastest first: the exact-2x marching kernel,
+// the pass kernels, the generic kernels. `raw` / `lout`: the call of an inner
+// plan by its owner (lancir_owner) -- `src` and `dst` may then be null, and
+// AVIRHIP_NEED_SRC / AVIRHIP_NEED_DST ask the owner for them. `stored`: the
+// last pass ran `lout` and stored the owner's pixels; otherwise the float
+// result is at `dst`.
+static int lancir_kernels( avirhip_plan* p, const float* src, float* dst,
+	int row0, int row1, hipStream_t st, const SrcWindow win,
+	const ImageRef* raw, const LancirOut* lout, bool& stored )
+{
+	const int lpath = ( p -> path != 0 ? p -> path : p -> auto_path );
+	int rc;
+
+	stored = false;
+
+	if( lpath == 4 )
+	{
+		if( dst == nullptr && lout == nullptr )
+		{
+			return( AVIRHIP_NEED_DST );
+		}
+
+		rc = lanc2_run( p, src, dst, row0, row1, st, win, raw, lout );
+
+		if( rc != 1 )
+		{
+			stored = ( rc == 0 && lout != nullptr );
+			return( rc );
+		}
+
+		if( raw != nullptr )
+		{
+			// (the kernels below would read the float copy the owner skipped)
+			return( AVIRHIP_NEED_SRC );
+		}
+
+		if( p -> path != 0 )
+		{
+			set_error( "path 4 cannot run this call (unaligned buffers?)" );
+			return( AVIRHIP_EUNSUPPORTED );
+		}
+	}
+
+	if( lpath == 5 || ( lpath == 4 && p -> path == 0 && gpass_ok( p )))
+	{
+		// general-ratio pass kernels (vertical pass first)
+		rc = gpass_run( p, src, p -> src_stride, dst, row0, row1, st, raw,
+			nullptr, lout );
+
+		if( rc != 1 )
+		{
+			stored = ( rc == 0 && lout != nullptr );
+			return( rc );
+		}
+
+		if( p -> path != 0 )
+		{
+			set_error( "path 5 cannot run this call (unaligned buffers?)" );
+			return( AVIRHIP_EUNSUPPORTED );
+		}
+	}
+
+	if( dst == nullptr )
+	{
+		return( AVIRHIP_NEED_DST );
+	}
+
+	// (the generic kernels' intermediate is only allocated when they run)
+	if(( rc = ensure_scratch( p )) != 0 ) return( rc );
+
+	return( launch_lancir_generic( p, src, dst, p -> resbuf, row0, row1, st ));
+}
+
+// A LANCIR plan with integer / scaled / 1-3 channel pixels (the owner): its
+// inner float RGBA plan's kernels between a pack pass and the output stage.
+// Where the inner kernels can, the first reads the owner's image as it lies
+// and the last stores the owner's pixels: the float RGBA copy of the source
+// (`packed`) and the float result (`lres`) are only allocated when a pass asks
+// for them -- 16 bytes per source and per destination pixel, per plan, spare
+// and replica, that also count against the plan cache. With the automatic path
+// of uint8 / uint16 images neither is touched.
+static int lancir_owner( avirhip_plan* p, const void* src, void* dst,
+	int row0, int row1, hipStream_t st )
+{
+	avirhip_plan* const q = p -> inner;
+	int rc;
+
+	if( row1 <= row0 )
+	{
+		return( AVIRHIP_OK );
+	}
+
+	// (double and uint32 elements, lancir.h:373-377: the pack pass and the
+	// output stage convert them; the fast kernels' own loaders and fused
+	// stores know uint8, uint16 and float)
+	const bool in_fast = ( p -> in_type <= AVIRHIP_F32 );
+	const bool out_fast = ( p -> out_type <= AVIRHIP_F32 );
+	const ImageRef img = { src, p -> in_type, p -> io_ch, p -> src_stride };
+	const LancirOut ostage = { dst, p -> new_stride, p -> out_type, p -> io_ch,
+		p -> l_unity, p -> l_out_mul, p -> l_clamp };
+
+	// k_lanc2's integer stage behind a raw RGBA source stores a lane's two
+	// elements at once
+	const bool dst2 = (( p -> io_ch == 3 || ( p -> new_stride & 1 ) == 0 ) &&
+		( p -> out_type != AVIRHIP_U8 || p -> io_ch == 3 ||
+		( (uintptr_t) dst & 1 ) == 0 ) &&
+		( p -> out_type != AVIRHIP_U16 ||
+		( (uintptr_t) dst & ( p -> io_ch == 3 ? 1 : 3 )) == 0 ) &&
+		( p -> out_type != AVIRHIP_F32 || ( (uintptr_t) dst & 3 ) == 0 ));
+
+	// the inner plan's first pass reads this image itself where it can;
+	// otherwise the pack pass makes its float RGBA copy
+	const ImageRef* raw = ( fused_io() && in_fast &&
+		( gpass_lancir_takes_raw( q, img ) ||
+		( lanc2_takes_raw( q, img ) && dst2 )) ? &img : nullptr );
+	const LancirOut* const lout = ( fused_io() && out_fast ? &ostage : nullptr );
+
+	auto pack = [&]() -> int
+	{
+		// the source rows this band's vertical windows read
+		int sa, sb;
+		band_src_rows( p, row0, row1, &sa, &sb );
+
+		const int r = need_floats( p, &p -> packed,
+			(size_t) p -> src_w * p -> src_h * 4 );
+
+		if( r != 0 ) return( r );
+
+		return( launch_pack( (const char*) src + (size_t) sa *
+			p -> src_stride * dtype_size( p -> in_type ), p -> in_type,
+			p -> packed + (size_t) sa * p -> src_w * 4, p -> src_w,
+			sb - sa + 1, p -> io_ch, 4, p -> src_stride, st ));
+	};
+
+	auto need_lres = [&]() -> int
+	{
+		return( need_floats( p, &p -> lres,
+			(size_t) p -> new_w * p -> new_h * 4 ));
+	};
+
+	if( raw == nullptr && ( rc = pack()) != 0 ) return( rc );
+
+	// (a null result buffer: only the fused store may run; a pass that would
+	// write the float result returns AVIRHIP_NEED_DST first)
+	if( lout == nullptr && ( rc = need_lres()) != 0 ) return( rc );
+
+	bool stored = false;
+
+	// (at most one round of each request: the kernel that was to read the
+	// owner's image refused the call -> float copy; a pass would have written
+	// the float result -> result buffer)
+	for( int round = 0; ; round++ )
+	{
+		rc = lancir_kernels( q, p -> packed, p -> lres, row0, row1, st,
+			SrcWindow{ 0, 0 }, raw, lout, stored );
+
+		if( rc != AVIRHIP_NEED_SRC && rc != AVIRHIP_NEED_DST )
+		{
+			break;
+		}
+
+		if( round == 2 )
+		{
+			set_error( "LANCIR: the inner plan kept asking for buffers (%d)", rc );
+			return( AVIRHIP_EINTERNAL );
+		}
+
+		if( rc == AVIRHIP_NEED_SRC )
+		{
+			raw = nullptr;
+			rc = pack();
+		}
+		else
+		{
+			rc = need_lres();
+		}
+
+		if( rc != 0 ) return( rc );
+	}
+
+	if( rc != 0 || stored )
+	{
+		return( rc );
+	}
+
+	if( p -> io_ch == 4 )
+	{
+		return( launch_lancir_out( p, p -> lres, (long) p -> new_w * 4, dst,
+			row1 - row0, st ));
+	}
+
+	return( launch_lancir_out_pad( p, p -> lres, dst, row1 - row0, st ));
+}
+
+// ---- AVIR ----
+
+// The source of one AVIR call: the caller's image, and the float image the
+// kernels read -- the caller's own (float pixels of the plan's channel count,
+// no gamma), or the plan's `packed` copy, which the pack pass fills at most
+// once per call and only when a kernel is about to read it.
+struct AvirSrc
+{
+	const void* img;
+	const float* f;
+	long fstride;
+	bool need_pack, packed;
+};
+
+static int avir_pack( avirhip_plan* p, AvirSrc& S, int row0, int row1,
+	hipStream_t st )
+{
+	if( !S.need_pack || S.packed )
+	{
+		return( AVIRHIP_OK );
+	}
+
+	S.packed = true;
+
+	// a band converts the source rows its windows read, nothing else (the
+	// pipelined host-pointer call is 16 bands: 16 whole-frame packs otherwise)
+	int pa, pb;
+	band_src_rows( p, row0, row1, &pa, &pb );
+
+	if( pb < pa )
+	{
+		return( AVIRHIP_OK );
+	}
+
+	const char* const ps = (const char*) S.img + (size_t) pa *
+		p -> src_stride * dtype_size( p -> in_type );
+	float* const pd = p -> packed + (size_t) pa * p -> src_w * p -> ch;
+
+	if( p -> gamma )
+	{
+		return( launch_pack_gamma( ps, p -> in_type, pd, p -> src_w,
+			pb - pa + 1, p -> io_ch, p -> ch, p -> src_stride,
+			p -> alpha_index, p -> d_srgb_tbl, st ));
+	}
+
+	return( launch_pack( ps, p -> in_type, pd, p -> src_w, pb - pa + 1,
+		p -> io_ch, p -> ch, p -> src_stride, st ));
+}
+
+// The fast paths of an AVIR call: 5 (pass kernels), 4 (exact-2x marching
+// kernel), 2 / 3 (LDS tiles). Returns 1 when the path cannot take the call
+// (the generic chain does), 0 when it ran: `stored` -- its last pass converted
+// and stored the caller's pixels at `dst`; otherwise the float result is at
+// `fdst`. `direct`: the caller's image IS the float result (fdst == dst).
+static int avir_fast( avirhip_plan* p, const int path, AvirSrc& S, void* dst,
+	float* fdst, const bool direct, int row0, int row1, hipStream_t st,
+	const SrcWindow win, bool& stored )
+{
+	int rc;
+	const ImageRef img = { S.img, p -> in_type, p -> io_ch, p -> src_stride };
+	const bool int_in = ( p -> in_type == AVIRHIP_U8 ||
+		p -> in_type == AVIRHIP_U16 );
+	const bool int_out = ( p -> out_type == AVIRHIP_U8 ||
+		p -> out_type == AVIRHIP_U16 );
+
+	// integer / narrow output without gamma / error diffusion: the last pass
+	// may convert and store into the caller's image itself (no float result,
+	// no epilogue pass)
+	const bool stores = ( !direct && !p -> gamma &&
+		(( p -> dither == AVIRHIP_DITHER_DEF && int_out ) ||
+		p -> out_type == AVIRHIP_F32 ) && fused_io());
+
+	// integer / narrower sources: the path's first kernel reads the caller's
+	// image as it lies, the float copy of the source (pack pass) is skipped --
+	// the tile loaders (2, 3), the streaming pass kernel (5), and the marching
+	// kernel (4) when it also stores the caller's integer pixels (it may still
+	// refuse the call -- alignment, a source window: the pack pass runs then)
+	const bool raw = ( !p -> gamma && p -> ch == 4 && ( path == 5 ?
+		S.need_pack && ( int_in || p -> in_type == AVIRHIP_F32 ) &&
+		gpass_takes_raw( p ) :
+		path == 4 ? S.need_pack && int_in &&
+		( p -> io_ch == 3 || p -> io_ch == 4 ) && int_out &&
+		p -> dither == AVIRHIP_DITHER_DEF && up2_stores_io( p ) && fused_io() :
+		int_in && fused_takes_raw( p, path )));
+
+	if( !raw && ( rc = avir_pack( p, S, row0, row1, st )) != 0 ) return( rc );
+
+	stored = false;
+
+	if( path == 5 )
+	{
+		void* iout = ( stores ? dst : nullptr );
+
+		for( ;; )
+		{
+			rc = ( raw ?
+				gpass_run( p, nullptr, 0, fdst, row0, row1, st, &img, iout,
+				nullptr ) :
+				gpass_run( p, S.f, S.fstride, fdst, row0, row1, st, nullptr,
+				iout, nullptr ));
+
+			if( rc != 1 || iout == nullptr )
+			{
+				stored = ( rc == 0 && iout != nullptr );
+				return( rc );
+			}
+
+			iout = nullptr; // this plan's last pass cannot: float result
+		}
+	}
+
+	if( path == 4 )
+	{
+		if( stores && raw )
+		{
+			rc = up2_run( p, nullptr, 0, nullptr, row0, row1, st, win, &img,
+				dst );
+
+			if( rc != 1 )
+			{
+				stored = ( rc == 0 ); // (no pack pass, no epilogue)
+				return( rc );
+			}
+		}
+
+		if(( rc = avir_pack( p, S, row0, row1, st )) != 0 ) return( rc );
+
+		if( stores )
+		{
+			rc = up2_run( p, S.f, S.fstride, nullptr, row0, row1, st, win,
+				nullptr, dst );
+
+			if( rc != 1 )
+			{
+				stored = ( rc == 0 );
+				return( rc );
+			}
+		}
+
+		return( up2_run( p, S.f, S.fstride, fdst, row0, row1, st, win,
+			nullptr, nullptr ));
+	}
+
+	// the tiles: the whole-ratio vertical kernel of the two-pass path stores
+	void* const iout = ( stores && !( p -> out_type == AVIRHIP_U8 &&
+		p -> io_ch == 4 && ( (uintptr_t) dst & 3 ) != 0 ) &&
+		fused_stores_int( p, path ) ? dst : nullptr );
+
+	rc = ( raw ?
+		fused_run( p, path, S.img, p -> in_type, p -> io_ch, p -> src_stride,
+		fdst, row0, row1, st, iout ) :
+		fused_run( p, path, S.f, AVIRHIP_F32, 4, S.fstride, fdst, row0, row1,
+		st, iout ));
+
+	stored = ( rc == 0 && iout != nullptr );
+	return( rc );
+}
+
+// The tail of an AVIR call whose float result is at `fdst` (and is not the
+// caller's image): error diffusion or the output stage into `dst`.
+static int avir_output( avirhip_plan* p, const float* fdst, void* dst,
+	int row0, int row1, hipStream_t st )
+{
+	if( p -> dither == AVIRHIP_DITHER_ERRD )
+	{
+		// recursive ditherer: whole frames only (exec_any refuses bands).
+		// One row of diffusion values per pass of 448 rows (generic.hip:
+		// k_errd_mp; the single-workgroup kernels use two), then the passes'
+		// progress flags
+		if( p -> errd_line == nullptr )
+		{
+			void* q;
+			const size_t np = (size_t) ( p -> new_h + 447 ) / 448 + 2;
+			const int rc = dev_alloc( p, np * p -> new_w * 4 * sizeof( float ) +
+				np * sizeof( unsigned ) + 64, &q );
+
+			if( rc != 0 ) return( rc );
+			p -> errd_line = (float*) q;
+		}
+
+		return( launch_errd( fdst, dst, p -> out_type, p -> new_w, p -> new_h,
+			p -> io_ch, p -> ch, p -> tr_mul, p -> pk_out, p -> gamma,
+			p -> alpha_index, p -> errd_line, st ));
+	}
+
+	return( launch_epilogue( fdst, dst, p -> out_type,
+		(long) ( row1 - row0 ) * p -> new_w * p -> io_ch, p -> tr_mul,
+		p -> pk_out, ( p -> gamma && ( p -> out_type != AVIRHIP_F32 ||
+		p -> fp4 )), p -> io_ch, p -> ch, p -> alpha_index, st,
+		p -> d_gthr, ( p -> dither == AVIRHIP_DITHER_DEF_RNE )));
+}
+
+static int exec_avir( avirhip_plan* p, const void* src, void* dst, int row0,
+	int row1, hipStream_t st, const SrcWindow win )
+{
+	int rc = ensure_scratch( p );
+	if( rc != 0 ) return( rc );
+
+	const int path = ( p -> path != 0 ? p -> path : p -> auto_path );
+	const bool need_pack = ( p -> gamma || p -> in_type != AVIRHIP_F32 ||
+		p -> ch != p -> io_ch );
+	AvirSrc S = { src, ( need_pack ? p -> packed : (const float*) src ),
+		( need_pack ? (long) p -> src_w * p -> ch : (long) p -> src_stride ),
+		need_pack, false };
+
+	// float output is the vertical pass' in-place result (avir.h:4956-4979):
+	// with gamma it stays linear, only the other output types are
+	// de-linearised in the epilogue
+	// (fpclass_float4 has no in-place output: its float results pass through
+	// the output stage like every other type, which matters with gamma)
+	const bool direct = ( p -> out_type == AVIRHIP_F32 &&
+		p -> ch == p -> io_ch && !( p -> fp4 && p -> gamma ));
+	float* const fdst = ( direct ? (float*) dst : p -> resbuf );
+
+	rc = 1;
+
+	if( path >= 2 && path <= 5 )
+	{
+		bool stored = false;
+		rc = avir_fast( p, path, S, dst, fdst, direct, row0, row1, st, win,
+			stored );
+
+		if( rc == 0 && stored )
+		{
+			return( AVIRHIP_OK ); // (no epilogue)
+		}
+
+		if( rc == 1 && p -> path != 0 )
+		{
+			set_error( "path %d cannot run this call (unaligned buffers?)",
+				path );
+			return( AVIRHIP_EUNSUPPORTED );
+		}
+	}
+
+	if( rc == 1 )
+	{
+		if(( rc = avir_pack( p, S, row0, row1, st )) != 0 ) return( rc );
+		rc = run_generic( p, S.f, S.fstride, fdst, row0, row1, st );
+	}
+
+	if( rc != 0 || direct )
+	{
+		return( rc );
+	}
+
+	return( avir_output( p, fdst, dst, row0, row1, st ));
+}
+
+// One call on device-resident buffers, by route.
+// `win`: a native source window (exec_any) -- `src` is then the virtual frame
+// base of the marching kernels, which are the only kernels such a call reaches
+static int exec_device( avirhip_plan* p, const void* src, void* dst,
+	int row0, int row1, hipStream_t st, const SrcWindow win )
+{
+	if( p -> f64 )
+	{
+		return( exec_f64( p, src, dst, row0, row1, st ));
+	}
+
+	if( !p -> is_lancir )
+	{
+		return( exec_avir( p, src, dst, row0, row1, st, win ));
+	}
+
+	if( p -> inner != nullptr && p -> path != 1 )
+	{
+		return( lancir_owner( p, src, dst, row0, row1, st ));
+	}
+
+	bool stored;
+	return( lancir_kernels( p, (const float*) src, (float*) dst, row0, row1,
+		st, win, nullptr, nullptr, stored ));
+}
+
+} // namespace avirhip
+
+// AVIRHIP_MEM_AUTO: device memory if the HIP runtime knows the pointer as such.
+extern "C" int avirhip_resolve_mem( const void* ptr, int mem )
+{
+	if( mem != AVIRHIP_MEM_AUTO )
+	{
+		return( mem );
+	}
+
+	hipPointerAttribute_t at;
+
+	if( ptr != nullptr && hipPointerGetAttributes( &at, ptr ) == hipSuccess &&
+		( at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged ))
+	{
+		return( AVIRHIP_MEM_DEVICE );
+	}
+
+	(void) hipGetLastError(); // unregistered host memory reports an error
+	return( AVIRHIP_MEM_HOST );
+}
+
+namespace avirhip {
+
+static int clone_plan( const avirhip_plan* s, int device, avirhip_plan** out );
+
 // Host-pointer call, pipelined (the call every existing caller of the
 // reference makes, avir.h:4680-4684): the frame in row bands, the source rows
 // of band b + 1 travelling host -> device (an uploader thread: a copy from
@@ -1307,9 +1323,6 @@ static int band_last_src_row( const avirhip_plan* p, int row0, int row1 )
 // computed and band b - 1 travels device -> host. PCIe is full duplex, so the
 // call costs the longer direction instead of the sum (cfg3: 531 MB down,
 // 133 MB up). Returns 1 when the call should take the serial path.
-static int exec_device( avirhip_plan* p, const void* src, void* dst,
-	int row0, int row1, hipStream_t st, const SrcWindow win );
-
 static int exec_host_pipelined( avirhip_plan* p, const void* src, void* dst,
 	size_t src_bytes, size_t dst_bytes, size_t row_bytes, hipStream_t st )
 {
@@ -1713,8 +1726,6 @@ static int exec_any( avirhip_plan* p, const void* src, int src_mem, void* dst,
 				if( clone_plan( p, p -> device, &spare ) == AVIRHIP_OK )
 				{
 					spare -> is_spare = 1;
-					spare -> path = p -> path;
-					spare -> variant = p -> variant;
 					spare -> exec_mtx.lock();
 					p -> spares.push_back( spare );
 				}
@@ -1856,14 +1867,8 @@ static int exec_any( avirhip_plan* p, const void* src, int src_mem, void* dst,
 	{
 		const size_t need = ( win_native ? win_bytes : src_bytes );
 
-		if( p -> stage_src_bytes < need )
-		{
-			void* q;
-			int rc = dev_alloc( p, need, &q );
-			if( rc != 0 ) return( rc );
-			p -> stage_src = q;
-			p -> stage_src_bytes = need;
-		}
+		const int rc = grow( p, &p -> stage_src, &p -> stage_src_bytes, need );
+		if( rc != 0 ) return( rc );
 
 		dsrc = p -> stage_src;
 	}
@@ -1901,14 +1906,9 @@ static int exec_any( avirhip_plan* p, const void* src, int src_mem, void* dst,
 	// while they write, so an overlapping device source is copied aside first.
 	if( overlap )
 	{
-		if( p -> stage_src_bytes < src_bytes )
-		{
-			void* q;
-			int rc = dev_alloc( p, src_bytes, &q );
-			if( rc != 0 ) return( rc );
-			p -> stage_src = q;
-			p -> stage_src_bytes = src_bytes;
-		}
+		const int rc = grow( p, &p -> stage_src, &p -> stage_src_bytes,
+			src_bytes );
+		if( rc != 0 ) return( rc );
 
 		AVIRHIP_HIPCHECK( hipMemcpyAsync( p -> stage_src, src, src_bytes,
 			hipMemcpyDeviceToDevice, st ));
@@ -1917,14 +1917,9 @@ static int exec_any( avirhip_plan* p, const void* src, int src_mem, void* dst,
 
 	if( dst_mem == AVIRHIP_MEM_HOST )
 	{
-		if( p -> stage_dst_bytes < dst_bytes )
-		{
-			void* q;
-			int rc = dev_alloc( p, dst_bytes, &q );
-			if( rc != 0 ) return( rc );
-			p -> stage_dst = q;
-			p -> stage_dst_bytes = dst_bytes;
-		}
+		const int rc = grow( p, &p -> stage_dst, &p -> stage_dst_bytes,
+			dst_bytes );
+		if( rc != 0 ) return( rc );
 
 		ddst = p -> stage_dst;
 	}
@@ -2044,8 +2039,6 @@ static avirhip_plan* new_plan()
 	p -> ch = 0; p -> io_ch = 0;
 	p -> l_out_mul = 1.0f; p -> l_clamp = 0.0f; p -> l_unity = 1;
 	p -> inner = nullptr; p -> l_order = 4;
-	memset( &p -> lfuse, 0, sizeof( p -> lfuse ));
-	memset( &p -> lraw, 0, sizeof( p -> lraw ));
 	(void) hipGetDevice( &p -> device );
 	return( p );
 }
@@ -2405,22 +2398,50 @@ static int clone_plan( const avirhip_plan* s, int device, avirhip_plan** out )
 		return( rc );
 	}
 
+	if( q -> inner != nullptr )
+	{
+		q -> inner -> path = q -> path;
+		q -> inner -> variant = q -> variant;
+	}
+
 	*out = hold.release();
 	return( AVIRHIP_OK );
 }
 
-static int grow( avirhip_plan* p, void** buf, size_t* have, size_t need )
+// The forced path and variant of a plan hold for everything that runs its
+// calls: its inner plan, its same-device spares and other-device replicas, and
+// their inner plans. They are pushed when they are set (and copied by
+// clone_plan), never per call.
+static void push_forced( avirhip_plan* p )
 {
-	if( *have < need )
+	const int path = p -> path;
+	const int variant = p -> variant;
+	auto set = [ path, variant ]( avirhip_plan* q )
 	{
-		void* q;
-		const int rc = dev_alloc( p, need, &q );
-		if( rc != 0 ) return( rc );
-		*buf = q;
-		*have = need;
-	}
+		for( ; q != nullptr; q = q -> inner )
+		{
+			q -> path = path;
+			q -> variant = variant;
+		}
+	};
 
-	return( AVIRHIP_OK );
+	set( p -> inner );
+	{
+		std::lock_guard< std::mutex > sl( p -> spare_mtx );
+
+		for( size_t i = 0; i < p -> spares.size(); i++ )
+		{
+			set( p -> spares[ i ]);
+		}
+	}
+	{
+		std::lock_guard< std::mutex > sl( p -> shard_mtx );
+
+		for( size_t i = 0; i < p -> replicas.size(); i++ )
+		{
+			set( p -> replicas[ i ]);
+		}
+	}
 }
 
 } // namespace avirhip
@@ -2856,28 +2877,7 @@ try
 	}
 
 	p -> path = path;
-
-	// the plan's same-device spares and other-device replicas run what it runs
-	{
-		std::lock_guard< std::mutex > sl( p -> spare_mtx );
-
-		for( size_t i = 0; i < p -> spares.size(); i++ )
-		{
-			p -> spares[ i ] -> path = path;
-		}
-	}
-	{
-		std::lock_guard< std::mutex > sl( p -> shard_mtx );
-
-		for( size_t i = 0; i < p -> replicas.size(); i++ )
-		{
-			if( p -> replicas[ i ] != nullptr )
-			{
-				p -> replicas[ i ] -> path = path;
-			}
-		}
-	}
-
+	push_forced( p );
 	return( AVIRHIP_OK );
 }
 AVIRHIP_CATCH( avirhip_plan_set_path )
@@ -2898,32 +2898,7 @@ try
 	}
 
 	p -> variant = variant;
-
-	if( p -> inner != nullptr )
-	{
-		p -> inner -> variant = variant;
-	}
-
-	{
-		std::lock_guard< std::mutex > sl( p -> spare_mtx );
-
-		for( size_t i = 0; i < p -> spares.size(); i++ )
-		{
-			p -> spares[ i ] -> variant = variant;
-		}
-	}
-	{
-		std::lock_guard< std::mutex > sl( p -> shard_mtx );
-
-		for( size_t i = 0; i < p -> replicas.size(); i++ )
-		{
-			if( p -> replicas[ i ] != nullptr )
-			{
-				p -> replicas[ i ] -> variant = variant;
-			}
-		}
-	}
-
+	push_forced( p );
 	return( AVIRHIP_OK );
 }
 AVIRHIP_CATCH( avirhip_plan_set_variant )

@@ -1371,9 +1371,12 @@ static void v_source_rows( const GPData* D, int row0, int row1, int& a, int& b )
 // by LDS-DMA, so the base and the row pitch have to be dword-aligned, the image
 // under 2 GiB, and the tap count one of the register-window variants of k_gv
 // (the LDS-window form keeps a ring of float pixels).
-bool gpass_lancir_takes_raw( const avirhip_plan* p, const void* raw, int type,
-	int ch, long stride )
+bool gpass_lancir_takes_raw( const avirhip_plan* p, const ImageRef& img )
 {
+	const void* const raw = img.ptr;
+	const int type = img.type;
+	const int ch = img.ch;
+	const long stride = img.stride;
 	const GPData* D = (const GPData*) p -> gpass;
 	const int lpath = ( p -> path != 0 ? p -> path : p -> auto_path );
 	const long esz = ( type == AVIRHIP_U8 ? 1 : ( type == AVIRHIP_U16 ? 2 : 4 ));
@@ -1411,12 +1414,28 @@ bool gpass_takes_raw( const avirhip_plan* p )
 		( D -> h_geom && D -> h_nseg <= 4 )));
 }
 
+// the owner's output stage (LancirOut) as the kernels' store parameters
+static GPLOut gp_make_lout( const avirhip_plan* p, const LancirOut& o )
+{
+	GPLOut L;
+	memset( &L, 0, sizeof( L ));
+	L.on = 1; L.type = o.type; L.ch = o.ch; L.unity = o.unity;
+	L.out_mul = o.out_mul; L.clampv = o.clampv;
+	L.l4 = ( p -> new_w * o.ch ) & ~3;
+	L.base = o.dst; L.stride = o.stride;
+	return( L );
+}
+
 // `iout` != nullptr: the caller's integer image (the band's first row) -- the
 // last pass converts and stores there (no float result, no epilogue pass);
 // returns 1 if this plan's last pass cannot (the caller then runs unfused).
+// `raw` != nullptr: the first pass reads that image as it lies instead of
+// `src` -- the caller's (AVIR) or the owner's (a LANCIR inner plan).
+// `lout` != nullptr (a LANCIR inner plan): the last pass runs the owner's
+// output stage and stores into its image; a return of 0 says that it has.
 int gpass_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
-	int row0, int row1, hipStream_t st, const void* raw, int raw_type,
-	int raw_ch, long raw_stride, void* iout )
+	int row0, int row1, hipStream_t st, const ImageRef* raw, void* iout,
+	const LancirOut* lout )
 {
 	GPOut O;
 	memset( &O, 0, sizeof( O ));
@@ -1445,7 +1464,7 @@ int gpass_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 	if( D == nullptr || ( iout == nullptr && ( (uintptr_t) dst & 15 )) ||
 		( p -> is_lancir && ( p -> new_stride & 3 )) ||
 		( raw == nullptr && (( (uintptr_t) src & 15 ) || ( src_stride & 3 ))) ||
-		( raw != nullptr && !gpass_takes_raw( p )))
+		( raw != nullptr && !p -> is_lancir && !gpass_takes_raw( p )))
 	{
 		return( 1 );
 	}
@@ -1489,13 +1508,13 @@ int gpass_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 	// profiles/r05_lanc, tools/rounds/r05_lf2.sh)
 	static const double lf_ratio = ( getenv( "AVIRHIP_LF_INT_RATIO" ) != nullptr ?
 		atof( getenv( "AVIRHIP_LF_INT_RATIO" )) : -1.0 ); // (tuning aid)
-	const bool lf_pays = ( !p -> lfuse.on || p -> lfuse.type == AVIRHIP_F32 ||
+	const bool lf_pays = ( lout == nullptr || lout -> type == AVIRHIP_F32 ||
 		(double) p -> new_w <= (double) p -> src_w * ( lf_ratio >= 0.0 ?
-		lf_ratio : ( p -> lfuse.ch == 4 ? 3.2 : 2.7 )) ||
+		lf_ratio : ( lout -> ch == 4 ? 3.2 : 2.7 )) ||
 		( p -> variant & AVIRHIP_VARIANT_UPG_FUSED ) != 0 );
 	const bool use_lf = ( p -> is_lancir && D -> lf_ow != 0 && lf_pays &&
-		( !p -> lraw.on || lfuse_takes_raw( p -> lraw.ptr, p -> lraw.type,
-		p -> lraw.ch, p -> lraw.stride, p -> src_h, p -> src_w )) &&
+		( raw == nullptr || lfuse_takes_raw( raw -> ptr, raw -> type,
+		raw -> ch, raw -> stride, p -> src_h, p -> src_w )) &&
 		( p -> variant & AVIRHIP_VARIANT_UPG_TWO_PASS ) == 0 );
 
 	if( D -> mid == nullptr && !use_gf && !use_lf )
@@ -1517,7 +1536,7 @@ int gpass_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 			return( 1 );
 		}
 
-		if( dst == nullptr && !p -> lfuse.on )
+		if( dst == nullptr && lout == nullptr )
 		{
 			return( AVIRHIP_NEED_DST );
 		}
@@ -1536,46 +1555,39 @@ int gpass_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 			G.nstrips = D -> lf_nstrips; G.ow = D -> lf_ow;
 			G.seg = D -> d_lfseg; G.vtab = D -> d_lfvtab;
 
-			if( p -> lraw.on )
+			if( raw != nullptr )
 			{
 				// (an inner plan: the owner's image, read as it is)
-				const int esz = ( p -> lraw.type == AVIRHIP_U8 ? 1 :
-					( p -> lraw.type == AVIRHIP_U16 ? 2 : 4 ));
+				const int esz = ( raw -> type == AVIRHIP_U8 ? 1 :
+					( raw -> type == AVIRHIP_U16 ? 2 : 4 ));
 
-				G.raw = p -> lraw.ptr; G.raw_ss = p -> lraw.stride;
+				G.raw = raw -> ptr; G.raw_ss = raw -> stride;
 				G.raw_kind = ( esz == 1 ? 1 : ( esz == 2 ? 2 : 3 ));
-				G.raw_ch = p -> lraw.ch; G.raw_bpp = esz * p -> lraw.ch;
+				G.raw_ch = raw -> ch; G.raw_bpp = esz * raw -> ch;
 				// (rounded up to whole dwords, as in gpass_run_v)
-				G.raw_bytes = (int) (((( (long) ( p -> src_h - 1 ) * p -> lraw.stride +
-					(long) p -> src_w * p -> lraw.ch ) * esz ) + 3 ) & ~3L );
+				G.raw_bytes = (int) (((( (long) ( p -> src_h - 1 ) * raw -> stride +
+					(long) p -> src_w * raw -> ch ) * esz ) + 3 ) & ~3L );
 				G.raw_tdn = ( 64 * G.raw_bpp + ( G.raw_bpp & 3 ? 3 : 0 ) + 255 ) >> 8;
 			}
 
-			if( p -> lfuse.on )
+			if( lout != nullptr )
 			{
-				G.lout.on = 1; G.lout.type = p -> lfuse.type;
-				G.lout.ch = p -> lfuse.ch; G.lout.unity = p -> lfuse.unity;
-				G.lout.out_mul = p -> lfuse.out_mul;
-				G.lout.clampv = p -> lfuse.clampv;
-				G.lout.l4 = ( p -> new_w * p -> lfuse.ch ) & ~3;
-				G.lout.base = p -> lfuse.dst; G.lout.stride = p -> lfuse.stride;
+				G.lout = gp_make_lout( p, *lout );
 			}
 
-			rc = lfuse_launch( G, st );
-			p -> lfuse.done = ( rc == 0 && p -> lfuse.on );
-			return( rc );
+			return( lfuse_launch( G, st ));
 		}
 
 		// vertical first (lancir.h:601-646): mid = [new_h][src_w], only the
 		// rows of the band
 		const long mid_ss = (long) p -> src_w * 4;
 
-		if( p -> lraw.on )
+		if( raw != nullptr )
 		{
 			// (an inner plan: the owner's image, read as it is)
 			rc = gpass_run_v( D -> v.a, D -> v_blk, D -> v_rs, D -> v_rc, src, src_stride, p -> src_w, D -> mid, mid_ss, 0,
-				row0, row1, st, nullptr, p -> lraw.ptr, p -> lraw.type,
-				p -> lraw.ch, p -> lraw.stride );
+				row0, row1, st, nullptr, raw -> ptr, raw -> type,
+				raw -> ch, raw -> stride );
 
 			// (the kernel refused the image after all: the owner makes the
 			// float copy and calls again)
@@ -1586,22 +1598,14 @@ int gpass_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 		if(( rc = gpass_run_v( D -> v.a, D -> v_blk, D -> v_rs, D -> v_rc, src, src_stride, p -> src_w, D -> mid, mid_ss, 0,
 			row0, row1, st )) != 0 ) return( rc );
 
-		if( p -> lfuse.on )
+		if( lout != nullptr )
 		{
 			// (an inner plan: the outer plan's output stage goes into the
 			// store of this pass, its result rows are never written)
-			GPLOut L;
-			memset( &L, 0, sizeof( L ));
-			L.on = 1; L.type = p -> lfuse.type; L.ch = p -> lfuse.ch;
-			L.unity = p -> lfuse.unity; L.out_mul = p -> lfuse.out_mul;
-			L.clampv = p -> lfuse.clampv;
-			L.l4 = ( p -> new_w * p -> lfuse.ch ) & ~3;
-			L.base = p -> lfuse.dst; L.stride = p -> lfuse.stride;
-			rc = run_h( D, D -> mid, mid_ss, p -> src_w, dst, dst_ss, row0,
-				p -> new_w, row0, row1, st, nullptr, 0, 0, 0, &L );
+			const GPLOut L = gp_make_lout( p, *lout );
 
-			p -> lfuse.done = ( rc == 0 );
-			return( rc );
+			return( run_h( D, D -> mid, mid_ss, p -> src_w, dst, dst_ss, row0,
+				p -> new_w, row0, row1, st, nullptr, 0, 0, 0, &L ));
 		}
 
 		if( dst == nullptr )
@@ -1645,6 +1649,11 @@ int gpass_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 	rc = 1;
 	// an integer image is finite, and so is the FltBuf made from it: both
 	// passes may take the branch-free form of the accumulation kernel
+	// (the caller's image, for the kernels below)
+	const void* const rawp = ( raw != nullptr ? raw -> ptr : nullptr );
+	const int raw_type = ( raw != nullptr ? raw -> type : 0 );
+	const int raw_ch = ( raw != nullptr ? raw -> ch : 0 );
+	const long raw_stride = ( raw != nullptr ? raw -> stride : 0 );
 	const bool int_src = ( raw != nullptr && ( raw_type == AVIRHIP_U8 ||
 		raw_type == AVIRHIP_U16 ));
 	const bool ladder = (( p -> variant & AVIRHIP_VARIANT_SACC_LADDER ) != 0 );
@@ -1695,7 +1704,7 @@ int gpass_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 		{
 			if( raw != nullptr )
 			{
-				return( sacc_run_axis( D -> sa_h, true, raw, raw_type, raw_ch,
+				return( sacc_run_axis( D -> sa_h, true, rawp, raw_type, raw_ch,
 					raw_ch, raw_stride * 4, raw_ch * 4, D -> mid, mid_ss, 4, a,
 					b + 1, 0, p -> new_w, st, nullptr, fast, false, fast,
 					fast ? D -> nf_flag : nullptr, fast ? nullptr : D -> nf_flag ));
@@ -1746,7 +1755,7 @@ int gpass_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 			const long es = ( raw_type == AVIRHIP_U8 ? 1 :
 				( raw_type == AVIRHIP_U16 ? 2 : 4 ));
 
-			rc = sacc_run_axis( D -> sa_h, true, raw, raw_type, raw_ch, raw_ch,
+			rc = sacc_run_axis( D -> sa_h, true, rawp, raw_type, raw_ch, raw_ch,
 				raw_stride * es, raw_ch * es, D -> mid, mid_ss, 4, a, b + 1, 0,
 				p -> new_w, st, nullptr, int_src, ladder );
 		}
@@ -1766,7 +1775,7 @@ int gpass_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 		}
 
 		rc = run_h( D, src, src_stride, p -> src_w, D -> mid, mid_ss, 0,
-			p -> new_w, a, b + 1, st, raw, raw_type, raw_ch, raw_stride );
+			p -> new_w, a, b + 1, st, rawp, raw_type, raw_ch, raw_stride );
 	}
 
 	if( rc != 0 ) return( rc );

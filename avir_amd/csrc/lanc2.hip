@@ -528,21 +528,30 @@ void lanc2_release( avirhip_plan* p )
 	p -> lanc2 = nullptr;
 }
 
-// Whether the exact-2x kernel of an inner plan reads its owner's image itself
-// (uint8 / uint16 RGBA; the conditions lanc2_run checks again).
-bool lanc2_takes_raw( const avirhip_plan* q, const void* raw, int type, int ch,
-	long stride )
+// The images k_lanc2 reads as they lie: uint8 / uint16 pixels of 3 or 4
+// channels in the plan's summation order, RGBA pixels inside aligned dwords,
+// row offsets that fit 31 bits. The ONE test behind lanc2_takes_raw's promise
+// and lanc2_run's refusal.
+static bool lanc2_raw_ok( const avirhip_plan* p, const ImageRef& raw )
+{
+	const int ch = raw.ch;
+	const int type = raw.type;
+
+	return(( ch == 4 || ch == 3 ) && ch == p -> l_order &&
+		( type == AVIRHIP_U8 || type == AVIRHIP_U16 ) &&
+		( ch == 3 || ( raw.stride & 1 ) == 0 ) &&
+		( (uintptr_t) raw.ptr & ( ch == 3 ? ( type == AVIRHIP_U8 ? 0 : 1 ) :
+		( type == AVIRHIP_U8 ? 1 : 3 ))) == 0 &&
+		(long) p -> src_h * raw.stride < ( 1L << 31 ));
+}
+
+// Whether the exact-2x kernel of an inner plan reads its owner's image itself.
+bool lanc2_takes_raw( const avirhip_plan* q, const ImageRef& raw )
 {
 	const int lpath = ( q -> path != 0 ? q -> path : q -> auto_path );
 
 	return( q -> lanc2 != nullptr && q -> is_lancir && lpath == 4 &&
-		( ch == 4 || ch == 3 ) && ch == q -> l_order &&
-		( type == AVIRHIP_U8 || type == AVIRHIP_U16 ) &&
-		( ch == 3 || ( stride & 1 ) == 0 ) &&
-		( (uintptr_t) raw & ( ch == 3 ? ( type == AVIRHIP_U8 ? 0 : 1 ) :
-		( type == AVIRHIP_U8 ? 1 : 3 ))) == 0 &&
-		(long) q -> src_h * stride < ( 1L << 31 ) &&
-		(long) q -> new_w * 4 < ( 1L << 30 ));
+		lanc2_raw_ok( q, raw ) && (long) q -> new_w * 4 < ( 1L << 30 ));
 }
 
 // The plain float RGBA call lanc2_run cannot refuse (its own checks with io ==
@@ -550,7 +559,7 @@ bool lanc2_takes_raw( const avirhip_plan* q, const void* raw, int type, int ch,
 bool lanc2_takes_window( const avirhip_plan* p, const void* src, const void* dst )
 {
 	return( p -> lanc2 != nullptr && p -> is_lancir && p -> inner == nullptr &&
-		!p -> lfuse.on && !p -> lraw.on && p -> ch == 4 && p -> io_ch == 4 &&
+		p -> ch == 4 && p -> io_ch == 4 &&
 		p -> in_type == AVIRHIP_F32 && p -> out_type == AVIRHIP_F32 &&
 		p -> l_unity && dst != nullptr &&
 		( (uintptr_t) src & 7 ) == 0 && ( (uintptr_t) dst & 7 ) == 0 &&
@@ -559,51 +568,50 @@ bool lanc2_takes_window( const avirhip_plan* p, const void* src, const void* dst
 		(long) p -> new_w * 4 < ( 1L << 30 ));
 }
 
-// p -> lfuse.on (an inner plan, set by its owner around the call): the
-// horizontal phase runs the owner's output stage and stores into its image;
-// dst is not used then. Sets p -> lfuse.done.
-int lanc2_run( avirhip_plan* p, const float* src, float* dst, int row0,
-	int row1, hipStream_t st, SrcWindow win )
+// `raw` / `lout` (an inner plan's call): the owner's image read as it lies
+// instead of `src`; the horizontal phase runs the owner's output stage and
+// stores into its image -- `dst` is not used then.
+int lanc2_run( const avirhip_plan* p, const float* src, float* dst, int row0,
+	int row1, hipStream_t st, SrcWindow win, const ImageRef* raw,
+	const LancirOut* lout )
 {
 	const Lanc2Data* D = (const Lanc2Data*) p -> lanc2;
-	const int io = ( !p -> lfuse.on ? 0 :
-		( p -> lfuse.type == AVIRHIP_U8 ? 1 :
-		( p -> lfuse.type == AVIRHIP_U16 ? 2 :
-		( p -> lfuse.type == AVIRHIP_F32 ? 3 : -1 ))));
+	const int io = ( lout == nullptr ? 0 :
+		( lout -> type == AVIRHIP_U8 ? 1 :
+		( lout -> type == AVIRHIP_U16 ? 2 :
+		( lout -> type == AVIRHIP_F32 ? 3 : -1 ))));
 
 	if( io < 0 || ( io == 0 && dst == nullptr ))
 	{
 		return( 1 );
 	}
 
-	// (an inner plan whose owner asked for its image to be read as it is)
-	const int sk = ( !p -> lraw.on ? 0 : ( p -> lraw.type == AVIRHIP_U8 ? 1 :
-		( p -> lraw.type == AVIRHIP_U16 ? 2 : -1 )));
+	if( raw != nullptr && !lanc2_raw_ok( p, *raw ))
+	{
+		return( 1 );
+	}
 
-	const bool r4 = ( p -> lraw.ch == 4 );
+	// (the source kind of the kernel: 0 float RGBA, 1 uint8, 2 uint16)
+	const int sk = ( raw == nullptr ? 0 : ( raw -> type == AVIRHIP_U8 ? 1 : 2 ));
+	const bool r4 = ( raw != nullptr && raw -> ch == 4 );
 
-	if( sk < 0 || ( sk != 0 && (( p -> lraw.ch != 4 && p -> lraw.ch != 3 ) ||
-		p -> lraw.ch != p -> l_order ||
-		( r4 && sk == 1 && ( (uintptr_t) p -> lraw.ptr & 1 )) ||
-		( r4 && ( p -> lraw.stride & 1 )) ||
-		( r4 && sk == 2 && ( (uintptr_t) p -> lraw.ptr & 3 )) ||
-		( !r4 && sk == 2 && ( (uintptr_t) p -> lraw.ptr & 1 )) ||
-		(long) p -> src_h * p -> lraw.stride >= ( 1L << 31 ) ||
-		( io != 0 && ( p -> lfuse.ch != p -> lraw.ch ||
-		( r4 && ( p -> lfuse.stride & 1 )) ||
-		( r4 && io == 1 && ( (uintptr_t) p -> lfuse.dst & 1 )) ||
-		( io == 2 && ( (uintptr_t) p -> lfuse.dst & ( r4 ? 3 : 1 ))))))))
+	// (the integer stage behind a raw RGBA source stores a lane's two elements
+	// at once)
+	if( sk != 0 && io != 0 && ( lout -> ch != raw -> ch ||
+		( r4 && ( lout -> stride & 1 )) ||
+		( r4 && io == 1 && ( (uintptr_t) lout -> dst & 1 )) ||
+		( io == 2 && ( (uintptr_t) lout -> dst & ( r4 ? 3 : 1 )))))
 	{
 		return( 1 );
 	}
 
 	if( D == nullptr || ( sk == 0 && ( (uintptr_t) src & 7 )) ||
 		( io == 0 && ( (uintptr_t) dst & 7 )) ||
-		( io == 2 && ( (uintptr_t) p -> lfuse.dst & 1 )) ||
-		( io == 3 && ( (uintptr_t) p -> lfuse.dst & 3 )) ||
+		( io == 2 && ( (uintptr_t) lout -> dst & 1 )) ||
+		( io == 3 && ( (uintptr_t) lout -> dst & 3 )) ||
 		// (the float image's pitch only matters when it is the one read: an
 		// inner plan reading its owner's integer image was checked on that
-		// image's pitch above, as lanc2_takes_raw() did)
+		// image's pitch above)
 		( sk == 0 && (( p -> src_stride & 1 ) ||
 		(long) p -> src_h * p -> src_stride >= ( 1L << 31 ))) ||
 		(long) p -> new_w * 4 >= ( 1L << 30 ))
@@ -626,11 +634,16 @@ int lanc2_run( avirhip_plan* p, const float* src, float* dst, int row0,
 	P.srow_lo = row0; P.srow_hi = row1;
 	P.nstrips = ( p -> new_w + L2_TW - 1 ) / L2_TW;
 	P.coef = D -> d_coef;
-	P.raw = p -> lraw.ptr; P.raw_ss = p -> lraw.stride; P.rch = p -> lraw.ch;
-	P.ibase = p -> lfuse.dst; P.istride = p -> lfuse.stride;
-	P.ich = p -> lfuse.ch; P.l4 = ( p -> new_w * p -> lfuse.ch ) & ~3;
-	P.unity = p -> lfuse.unity; P.out_mul = p -> lfuse.out_mul;
-	P.clampv = p -> lfuse.clampv;
+	// (what a kernel form without a raw source / an output stage never reads)
+	static const ImageRef no_raw = { nullptr, 0, 0, 0 };
+	static const LancirOut no_out = { nullptr, 0, 0, 0, 0, 0.0f, 0.0f };
+	const ImageRef& R = ( raw != nullptr ? *raw : no_raw );
+	const LancirOut& O = ( lout != nullptr ? *lout : no_out );
+	P.raw = R.ptr; P.raw_ss = R.stride; P.rch = R.ch;
+	P.ibase = O.dst; P.istride = O.stride;
+	P.ich = O.ch; P.l4 = ( p -> new_w * O.ch ) & ~3;
+	P.unity = O.unity; P.out_mul = O.out_mul;
+	P.clampv = O.clampv;
 
 	// chunk = 8k - 6 source rows (6 warm-up rows per chunk); fill whole rounds
 	// of 256 CUs x 8 resident workgroups with chunks of >= 58 rows
@@ -683,7 +696,6 @@ int lanc2_run( avirhip_plan* p, const float* src, float* dst, int row0,
 #undef L2_LAUNCH
 
 	AVIRHIP_HIPCHECK( hipGetLastError() );
-	p -> lfuse.done = ( io != 0 );
 	return( AVIRHIP_OK );
 }
 

@@ -51,8 +51,8 @@ __device__ __forceinline__ float avirhip_x86_round_fix( const float a,
 // internal: an inner plan was run without a float result buffer and its path
 // would have written one (exec_device allocates it and runs again)
 #define AVIRHIP_NEED_DST 1001
-// internal: an inner plan was told to read its owner's image as it is
-// (lraw.on) and the kernel that would have done so refused the call: the owner
+// internal: an inner plan was handed its owner's image to read as it is (an
+// ImageRef) and the kernel that would have done so refused the call: the owner
 // runs the pack pass and calls again with the float copy
 #define AVIRHIP_NEED_SRC 1002
 
@@ -161,11 +161,6 @@ struct avirhip_plan
 	// output stage (nullptr: this plan runs its own kernels)
 	avirhip_plan* inner;
 	int l_order; // LANCIR: channel count whose summation order the kernels use
-	// (set on an INNER plan by its owner around a call: the owner's output
-	// stage, fused into the last pass when that is a pass kernel)
-	struct { int on, done, type, ch, unity; float out_mul, clampv; void* dst;
-		long stride; } lfuse;
-	struct { int on, type, ch; const void* ptr; long stride; } lraw;
 
 	int path;       // forced path (0 = auto)
 	int variant;    // AVIRHIP_VARIANT_* bits (0 = automatic kernel forms)
@@ -217,12 +212,40 @@ struct avirhip_plan
 
 namespace avirhip {
 
+// What belongs to ONE call travels as an argument of that call, from exec_any
+// down to the *_run functions, never as state of the plan: plans are shared
+// between threads, and some whole-frame calls run without the plan's lock.
+
+// A caller's image as it lies in device memory: element type (AVIRHIP_U8 ...),
+// channels per pixel, row pitch in elements. A kernel family that is handed
+// one (`raw`, nullptr = none) reads it instead of the float RGBA copy a pack
+// pass would make.
+struct ImageRef
+{
+	const void* ptr;
+	int type, ch;
+	long stride;
+};
+
+// The output stage of a LANCIR plan with integer / scaled / 1-3 channel pixels
+// (the owner), handed to the kernels of its inner float RGBA plan (`lout`,
+// nullptr = none): the last pass applies gain and clamp, converts and stores
+// into the owner's image -- `dst` is the band's first row there -- and no float
+// result is written. lanc2_run and gpass_run that return 0 for a call with a
+// `lout` HAVE stored the owner's pixels: what they cannot store they refuse
+// (1, AVIRHIP_NEED_*).
+struct LancirOut
+{
+	void* dst;
+	long stride;
+	int type, ch, unity;
+	float out_mul, clampv;
+};
+
 // avirhip_resize_window on the marching kernels (k_up2, k_lanc2): the source
 // pointer handed to them is a VIRTUAL frame base -- window - first rows -- and
 // only rows [first, first + rows) exist behind it: the kernels clamp their row
-// indices to that range instead of [0, src_h). An argument of the call, from
-// exec_any down to up2_run / lanc2_run, never state of the plan: whole-frame
-// calls of the same plan run beside a window call without the plan's lock.
+// indices to that range instead of [0, src_h).
 // (rows == 0: the whole frame)
 struct SrcWindow
 {
@@ -370,7 +393,7 @@ void fused_release( avirhip_plan* p );
 // loader itself -- no pack pass). `src_stride` in elements of that type.
 int fused_run( avirhip_plan* p, int mode, const void* src, int src_type,
 	int src_ch, long src_stride, float* dst, int row0, int row1,
-	hipStream_t st, void* iout = nullptr );
+	hipStream_t st, void* iout );
 bool fused_stores_int( const avirhip_plan* p, int mode );
 bool fused_takes_raw( const avirhip_plan* p, int mode );
 
@@ -395,21 +418,21 @@ void gpass_release( avirhip_plan* p );
 bool gpass_ok( const avirhip_plan* p );
 bool gpass_preferred( const avirhip_plan* p );
 bool gpass_takes_raw( const avirhip_plan* p );
-bool gpass_lancir_takes_raw( const avirhip_plan* p, const void* raw, int type,
-	int ch, long stride );
+bool gpass_lancir_takes_raw( const avirhip_plan* p, const ImageRef& raw );
+// `raw`: the image the first pass reads instead of `src`; `iout`: the last pass
+// of an AVIR plan stores the caller's pixels there; `lout`: the last pass of a
+// LANCIR inner plan runs its owner's output stage
 int gpass_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
-	int row0, int row1, hipStream_t st, const void* raw = nullptr,
-	int raw_type = 0, int raw_ch = 0, long raw_stride = 0,
-	void* iout = nullptr );
+	int row0, int row1, hipStream_t st, const ImageRef* raw, void* iout,
+	const LancirOut* lout );
 bool fused_dn_both( const avirhip_plan* p );
 
 // up2.hip: specialised exact-2x RGBA kernel (path 4)
 int up2_prepare( avirhip_plan* p );
 void up2_release( avirhip_plan* p );
 int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
-	int row0, int row1, hipStream_t st, void* iout = nullptr,
-	const void* raw = nullptr, long raw_stride = 0,
-	SrcWindow win = SrcWindow{ 0, 0 });
+	int row0, int row1, hipStream_t st, SrcWindow win, const ImageRef* raw,
+	void* iout );
 bool up2_stores_io( const avirhip_plan* p );
 // whether up2_run / lanc2_run take this float RGBA call for certain (no refusal,
 // no fall-back to kernels that know nothing of a source window)
@@ -419,9 +442,9 @@ bool lanc2_takes_window( const avirhip_plan* p, const void* src, const void* dst
 // lanc2.hip: LANCIR exact-2x RGBA float kernel (path 4 of LANCIR plans)
 int lanc2_prepare( avirhip_plan* p );
 void lanc2_release( avirhip_plan* p );
-int lanc2_run( avirhip_plan* p, const float* src, float* dst, int row0,
-	int row1, hipStream_t st, SrcWindow win = SrcWindow{ 0, 0 });
-bool lanc2_takes_raw( const avirhip_plan* q, const void* raw, int type, int ch,
-	long stride );
+int lanc2_run( const avirhip_plan* p, const float* src, float* dst, int row0,
+	int row1, hipStream_t st, SrcWindow win, const ImageRef* raw,
+	const LancirOut* lout );
+bool lanc2_takes_raw( const avirhip_plan* q, const ImageRef& raw );
 
 } // namespace avirhip

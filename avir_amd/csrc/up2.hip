@@ -1555,12 +1555,14 @@ bool up2_takes_window( const avirhip_plan* p, const void* src, const void* dst )
 // pass); returns 1 if this plan's form of the kernel cannot (the caller then
 // runs with a float result).
 // `raw` != nullptr (with `iout`): the caller's integer image (uint8 / uint16,
-// 3 or 4 channels, `raw_stride` elements per row) instead of `src`; returns 1
-// if this call cannot take it (the caller then packs and calls again).
+// 3 or 4 channels) instead of `src`; returns 1 if this call cannot take it
+// (the caller then packs and calls again).
 int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
-	int row0, int row1, hipStream_t st, void* iout, const void* raw,
-	long raw_stride, SrcWindow win )
+	int row0, int row1, hipStream_t st, SrcWindow win, const ImageRef* rawimg,
+	void* iout )
 {
+	const void* const raw = ( rawimg != nullptr ? rawimg -> ptr : nullptr );
+	const long raw_stride = ( rawimg != nullptr ? rawimg -> stride : 0 );
 	const Up2Data* D = (const Up2Data*) p -> up2;
 	static const bool novt = ( getenv( "AVIRHIP_UP2_NOVT" ) != nullptr );
 	int io = 0;
