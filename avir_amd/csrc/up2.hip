@@ -19,9 +19,10 @@
 //   S   U2_RB source rows x 50 px (halo 9+9): HBM -> LDS by LDS-DMA
 //       (buffer_load_dwordx4 ... lds), no staging registers
 //   H1  C rows  = FIR7 along x, whole pixels                     LDS -> LDS
-//   H2  T rows  = 12-tap even/odd interpolation along x (one source pixel
-//       = two whole output pixels per thread, one 13-pixel window of 128-bit
-//       LDS reads)                                               LDS -> LDS
+//   H2  T rows  = 12-tap even/odd interpolation along x (a thread streams
+//       once over a row's C half pixels and feeds the 8 sums of four source
+//       pixels U2_HS apart: a tap product shared by an even and an odd sum
+//       is multiplied once -- see h2_phase)                      LDS -> LDS
 //   V   each thread owns ONE HALF-PIXEL output column (8 bytes) and keeps the
 //       vertical FIR window (7) and the vertical interpolation window (13) in
 //       REGISTERS, rotating through statically-indexed ring slots (the 16-row
@@ -56,6 +57,9 @@ typedef unsigned u2 __attribute__(( ext_vector_type( 2 )));
 #define U2_NT ( U2_TW * 2 ) // threads per workgroup: one per half pixel
 #ifndef U2_RB
 #define U2_RB 8   // source rows per marching step (8 or 16)
+#endif
+#ifndef U2_HS
+#define U2_HS 4   // H2 (transposed form): distance of a thread's four source pixels (2 or 4)
 #endif
 #define U2_SW ( U2_TW / 2 + 18 ) // S tile width (px)
 #define U2_CW ( U2_TW / 2 + 12 ) // C tile width (px)
@@ -147,22 +151,22 @@ __device__ __forceinline__ Taps load_taps( const float* p0 )
 	return( t );
 }
 
-// packed fe0..11 and fo0..11 (the horizontal interpolation: 24 SGPRs)
+// packed fe0..11 (the horizontal interpolation: a bit-symmetric bank phase,
+// fo[t] == fe[11-t], needs no fo -- 12 SGPRs)
 struct TapsI
 {
-	f16 a; // fe0..11 fo0..3
-	f8 b;  // fo4..11
-	__device__ __forceinline__ f2 fe( int i ) const { return( splat( a[ i ])); }
-	__device__ __forceinline__ f2 fo( int i ) const
-		{ return( splat( i < 4 ? a[ 12 + i ] : b[ i - 4 ])); }
+	f8 a; // fe0..7
+	f4 b; // fe8..11
+	__device__ __forceinline__ f2 fe( int i ) const
+		{ return( splat( i < 8 ? a[ i ] : b[ i - 8 ])); }
 };
 
 __device__ __forceinline__ TapsI load_taps_i( const float* p0 )
 {
 	const float* const p = sgpr_ptr( p0 );
 	TapsI t;
-	asm volatile( "s_load_dwordx16 %0, %2, 0x10\n\t"
-		"s_load_dwordx8 %1, %2, 0x50\n\t"
+	asm volatile( "s_load_dwordx8 %0, %2, 0x10\n\t"
+		"s_load_dwordx4 %1, %2, 0x30\n\t"
 		AVIRHIP_WAITCNT_LGKM( 0 )
 		: "=&s"( t.a ), "=&s"( t.b ) : "s"( p ) : "memory" );
 	return( t );
@@ -292,12 +296,18 @@ __device__ __forceinline__ void u2_setprio( const int p )
 
 #define U2_TPL ( U2_RB * ( U2_TW / 2 ) + 8 ) // px per T plane, incl. the 128-B skew
 
+#ifndef U2_H2PB
+#define U2_H2PB 4 // H2 (transposed form): stream positions per block of LDS reads
+#endif
+
 // VT ("vertical transposed"): when the bank phase is bit-symmetric (fo[t] ==
 // fe[11-t], true for every parameter preset), the product fe[t]*C2[m] belongs to
 // BOTH even(m+3-t) and odd(m-9+t). The vertical phase then keeps 24 running
 // sums per thread instead of a 13-row window: each new C2 row costs 12
 // multiplies + 24 adds instead of 24 + 24, every sum still receives its
-// products in ascending tap order from a +0 start => same bits.
+// products in ascending tap order from a +0 start => same bits. The
+// horizontal interpolation of this form shares products the same way
+// (h2_phase), so it wants both axes' bank phases symmetric.
 // IO (VT only): 0 the float RGBA result; 1 uint8, 2 uint16, 3 float pixels of
 // P.ich channels stored by the vertical phase itself (a lane holds two
 // channels of a pixel: one store per channel, lanes without one carry an
@@ -424,10 +434,10 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 	// vector instructions of a marching step).
 	constexpr int RPI0 = U2_NT / U2_SW;
 	constexpr int CN0 = U2_RB * U2_CW;
-	unsigned pkA = 0; // lo: H2 window start in sC; hi: this half pixel in sT
+	unsigned pkA = 0; // lo: H2 stream start in sC; hi: this half pixel in sT
 	unsigned pkB = 0; // H1 iterations 0 / 1: first source pixel in sS
 	unsigned pkC = 0; // H1 iteration 2: source in sS / destination in sC
-	unsigned t16 = 0; // thread index * 16 (flat pixel slot in sC / sT)
+	unsigned pkD = 0; // lo: H1 iteration 0's destination in sC; hi: H2's first sum in sT
 	int pvoff = -1;   // source byte offset of this lane's DMA pixel (< 0: none)
 	int dlv = 0;      // destination byte offset within a row
 	int dlv2 = 0;     // IO != 0: ... of the lane's second channel
@@ -456,11 +466,23 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 			dlv = ( xo < P.nw ? ( xo * 4 + hf * 2 ) * 4 : (int) 0x80000000u );
 		}
 
-		t16 = (unsigned) tid * 16;
-		pkA = la( &sC[ ( tid / ( U2_TW / 2 )) * U2_CW +
-			( tid & ( U2_TW / 2 - 1 ))]) |
-			( la( (const f2*) sT + ((( col & 1 ) * U2_TPL + ( col >> 1 )) * 2 +
-			hf )) << 16 );
+		// H2's lanes: half pixel, first pixel within its group, row (low two
+		// bits), group of 4 * U2_HS pixels; a wave takes four rows. With
+		// U2_HS == 4 a 32-lane half of ds_read_b64 is one group x four rows
+		// (pitch 704 B: 0, 192, 128, 64 mod 256 B) of 64-byte runs: no bank
+		// conflict. (U2_HS == 2: 32-byte runs, 2-way in every lane order.)
+		{
+			constexpr int LS = ( U2_HS == 4 ? 2 : 1 );
+			const int hr = ( tid >> 6 ) * 4 + (( tid >> ( 1 + LS )) & 3 );
+			const int hq = (( tid >> ( 3 + LS )) & ( 8 / U2_HS - 1 )) * 4 * U2_HS +
+				(( tid >> 1 ) & ( U2_HS - 1 ));
+
+			pkA = la( (const f2*) &sC[ hr * U2_CW + hq ] + hf ) |
+				( la( (const f2*) sT + ((( col & 1 ) * U2_TPL + ( col >> 1 )) * 2 +
+				hf )) << 16 );
+			pkD = la( &sC[ tid ]) |
+				( la( (const f2*) &sT[ hr * ( U2_TW / 2 ) + hq ] + hf ) << 16 );
+		}
 
 		unsigned ha[ 3 ], hd = 0;
 #pragma unroll
@@ -474,7 +496,7 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 
 		pkB = ha[ 0 ] | ( ha[ 1 ] << 16 );
 		pkC = ha[ 2 ] | ( hd << 16 );
-		asm volatile( "" : "+v"( pkA ), "+v"( pkB ), "+v"( pkC ), "+v"( t16 ),
+		asm volatile( "" : "+v"( pkA ), "+v"( pkB ), "+v"( pkC ), "+v"( pkD ),
 			"+v"( pvoff ), "+v"( dlv ));
 
 		if constexpr( IO != 0 )
@@ -486,6 +508,7 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 	typedef const __attribute__(( address_space( 3 ))) f4* lds_cf4;
 	typedef __attribute__(( address_space( 3 ))) f4* lds_f4;
 	typedef const __attribute__(( address_space( 3 ))) f2* lds_cf2;
+	typedef __attribute__(( address_space( 3 ))) f2* lds_f2;
 	auto lo16 = []( const unsigned v ) -> unsigned
 	{
 		unsigned r;
@@ -696,8 +719,8 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 	{
 		const unsigned sa = ( k == 0 ? lo16( pkB ) : k == 1 ? hi16( pkB ) :
 			lo16( pkC ));
-		const unsigned da = ( k == 2 ? hi16( pkC ) : t16 + k * U2_NT * 16 +
-			(unsigned) (unsigned long long) (ldsptr) sC );
+		const unsigned da = ( k == 2 ? hi16( pkC ) :
+			lo16( pkD ) + k * U2_NT * 16 );
 		const lds_cf4 s = (lds_cf4) (unsigned long long) sa;
 		const f4 s0 = s[ 0 ], s1 = s[ 1 ], s2 = s[ 2 ], s3 = s[ 3 ];
 		const f4 s4 = s[ 4 ], s5 = s[ 5 ], s6 = s[ 6 ];
@@ -708,61 +731,101 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 		*(lds_f4) (unsigned long long) da = a;
 	};
 
-	// ---- H2: T[2q], T[2q+1] from the 13-px window C[qq .. qq+12], one source
-	// pixel (two whole output pixels) per thread and iteration
+	// ---- H2: T[2q], T[2q+1] = 12-tap even / odd interpolation of C along x.
+	// Transposed form: the bank phase is bit-symmetric, so the product
+	// fe[t]*C[m] belongs to even( m+3-t ) and to odd( m-9+t ), outputs of two
+	// source pixels 12 - 2t apart. A thread owns one half pixel of the four
+	// source pixels q0 + i * U2_HS of one row -- 8 running sums -- and streams
+	// once, in ascending order, over the 3 * U2_HS + 13 half pixels
+	// C[q0-3 .. q0+3*U2_HS+9]: at stream position k the even sum i takes tap
+	// k - i*U2_HS and the odd sum j takes fe[12 - k + j*U2_HS] (its own tap
+	// k - j*U2_HS - 1); a tap index wanted by an even and an odd sum at the
+	// same position is multiplied once: 81 (U2_HS 4) or 80 (U2_HS 2) packed
+	// multiplies for the 96 products. Every sum starts from +0 and receives
+	// the same products in the same (ascending tap) order as a sum of its own
+	// => same bits. Plain form: one source pixel (two whole output pixels) per
+	// thread and iteration from a 13-px window.
 	auto h2_phase = [&]()
 	{
 		if( VT && U2_ON( 2 ))
 		{
 			const TapsI H = load_taps_i( P.coef );
-			const lds_cf4 c0 = (lds_cf4) (unsigned long long) lo16( pkA );
-			const lds_f4 t0 = (lds_f4) (unsigned long long)
-				( t16 + (unsigned) (unsigned long long) (ldsptr) sT );
-			constexpr int RS = U2_NT / ( U2_TW / 2 ); // rows per iteration
+			const lds_cf2 c = (lds_cf2) (unsigned long long) lo16( pkA );
+			const lds_f2 t0 = (lds_f2) (unsigned long long) hi16( pkD );
+			constexpr int NP = 3 * U2_HS + 13; // stream positions
+			constexpr int PB = U2_H2PB;        // ... per block of LDS reads
+			constexpr int NB = ( NP + PB - 1 ) / PB;
+			f2 e[ 4 ], o[ 4 ];
+			f2 w[ 2 ][ PB ];
 
 #pragma unroll
-			for( int it = 0; it < U2_RB / RS; it++ )
+			for( int i = 0; i < 4; i++ ) e[ i ] = o[ i ] = (f2) 0.0f;
+#pragma unroll
+			for( int k = 0; k < PB; k++ ) w[ 0 ][ k ] = c[ k * 2 ];
+
+			// the stream in blocks: the next block's reads are in flight
+			// while this one is consumed (the transposed vertical phase keeps
+			// 64 registers live across this phase)
+#pragma unroll
+			for( int b = 0; b < NB; b++ )
 			{
-				const lds_cf4 c = c0 + it * RS * U2_CW;
-				f4 e = (f4) 0.0f;
-				f4 o = (f4) 0.0f;
-				f4 w[ 13 ];
-
-				// the window in three parts of 5 + 4 + 4 pixels: the
-				// transposed vertical phase keeps 64 registers live
-				// across this phase
 #pragma unroll
-				for( int t = 0; t < 5; t++ ) w[ t ] = c[ t ];
-#pragma unroll
-				for( int t = 0; t < 4; t++ )
+				for( int k = 0; k < PB; k++ )
 				{
-					e = e + tmul( H.fe( t ), w[ t ]);
-					o = o + tmul( H.fo( t ), w[ t + 1 ]);
+					if(( b + 1 ) * PB + k < NP )
+					{
+						w[ ( b + 1 ) & 1 ][ k ] = c[ (( b + 1 ) * PB + k ) * 2 ];
+					}
+				}
+
+#pragma unroll
+				for( int kk = 0; kk < PB; kk++ )
+				{
+					const int k = b * PB + kk;
+#pragma unroll
+					for( int t = 0; t < 12; t++ )
+					{
+						bool any = false;
+#pragma unroll
+						for( int i = 0; i < 4; i++ )
+						{
+							any |= ( k < NP && ( k - i * U2_HS == t ||
+								12 - k + i * U2_HS == t ));
+						}
+
+						if( any )
+						{
+							const f2 pr = H.fe( t ) * w[ b & 1 ][ kk ];
+#pragma unroll
+							for( int i = 0; i < 4; i++ )
+							{
+								if( k - i * U2_HS == t ) e[ i ] = e[ i ] + pr;
+								if( 12 - k + i * U2_HS == t ) o[ i ] = o[ i ] + pr;
+							}
+						}
+					}
+				}
+
+				// pin the sums that have begun, and the order of the reads,
+				// here: the sums are eight independent chains, and nothing
+				// else keeps the compiler from issuing the whole stream's
+				// reads first (50 registers)
+				asm volatile( "" ::: "memory" );
+#pragma unroll
+				for( int i = 0; i < 4; i++ )
+				{
+					if( i * U2_HS < ( b + 1 ) * PB ) asm volatile( "" : "+v"( e[ i ]));
+					if( i * U2_HS + 1 < ( b + 1 ) * PB ) asm volatile( "" : "+v"( o[ i ]));
 				}
 
 				__builtin_amdgcn_sched_barrier( 0 );
-#pragma unroll
-				for( int t = 5; t < 9; t++ ) w[ t ] = c[ t ];
-#pragma unroll
-				for( int t = 4; t < 8; t++ )
-				{
-					e = e + tmul( H.fe( t ), w[ t ]);
-					o = o + tmul( H.fo( t ), w[ t + 1 ]);
-				}
+			}
 
-				__builtin_amdgcn_sched_barrier( 0 );
 #pragma unroll
-				for( int t = 9; t < 13; t++ ) w[ t ] = c[ t ];
-#pragma unroll
-				for( int t = 8; t < 12; t++ )
-				{
-					e = e + tmul( H.fe( t ), w[ t ]);
-					o = o + tmul( H.fo( t ), w[ t + 1 ]);
-				}
-
-				t0[ it * U2_NT ] = e;
-				t0[ U2_TPL + it * U2_NT ] = o;
-				__builtin_amdgcn_sched_barrier( 0 );
+			for( int i = 0; i < 4; i++ )
+			{
+				t0[ i * U2_HS * 2 ] = e[ i ];
+				t0[ ( U2_TPL + i * U2_HS ) * 2 ] = o[ i ];
 			}
 		}
 		else
@@ -1446,7 +1509,18 @@ struct Up2Data
 	Up2Axis h, v;
 	float* d_coef;
 	bool vsym; // vertical bank phase bit-symmetric: fo[t] == fe[11-t]
+	bool hsym; // ... and the horizontal one
 };
+
+// Whether the plan runs the transposed form k_up2< true, ... >: both axes'
+// tap products are shared between an even and an odd sum there.
+static bool up2_vt( const avirhip_plan* p, const Up2Data* D )
+{
+	static const bool novt = ( getenv( "AVIRHIP_UP2_NOVT" ) != nullptr );
+
+	return( D != nullptr && U2_RB == 8 && D -> vsym && D -> hsym && !novt &&
+		!( p -> variant & AVIRHIP_VARIANT_UP2_PLAIN_V ));
+}
 
 int up2_prepare( avirhip_plan* p )
 {
@@ -1492,10 +1566,13 @@ int up2_prepare( avirhip_plan* p )
 			hipMemcpyHostToDevice ));
 		D -> d_coef = (float*) q;
 		D -> vsym = true;
+		D -> hsym = true;
 
 		for( int t = 0; t < 12; t++ )
 		{
 			D -> vsym &= ( memcmp( &D -> v.fo[ t ], &D -> v.fe[ 11 - t ],
+				sizeof( float )) == 0 );
+			D -> hsym &= ( memcmp( &D -> h.fo[ t ], &D -> h.fe[ 11 - t ],
 				sizeof( float )) == 0 );
 		}
 
@@ -1524,10 +1601,8 @@ void up2_release( avirhip_plan* p )
 bool up2_stores_io( const avirhip_plan* p )
 {
 	const Up2Data* D = (const Up2Data*) p -> up2;
-	static const bool novt = ( getenv( "AVIRHIP_UP2_NOVT" ) != nullptr );
 
-	return( D != nullptr && U2_RB == 8 && D -> vsym && !novt &&
-		!( p -> variant & AVIRHIP_VARIANT_UP2_PLAIN_V ) && !p -> gamma &&
+	return( up2_vt( p, D ) && !p -> gamma &&
 		p -> dither == AVIRHIP_DITHER_DEF &&
 		(( p -> out_type == AVIRHIP_U8 && p -> tr_mul == 1.0 &&
 		p -> pk_out == 255.0 ) ||
@@ -1564,13 +1639,11 @@ int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 	const void* const raw = ( rawimg != nullptr ? rawimg -> ptr : nullptr );
 	const long raw_stride = ( rawimg != nullptr ? rawimg -> stride : 0 );
 	const Up2Data* D = (const Up2Data*) p -> up2;
-	static const bool novt = ( getenv( "AVIRHIP_UP2_NOVT" ) != nullptr );
 	int io = 0;
 
 	if( iout != nullptr )
 	{
-		const bool vt = ( D != nullptr && U2_RB == 8 && D -> vsym && !novt &&
-			!( p -> variant & AVIRHIP_VARIANT_UP2_PLAIN_V ));
+		const bool vt = up2_vt( p, D );
 
 		io = ( p -> out_type == AVIRHIP_U8 && p -> tr_mul == 1.0 &&
 			p -> pk_out == 255.0 ? 1 :
@@ -1776,8 +1849,7 @@ int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 		}
 	}
 	else
-	if( U2_RB == 8 && D -> vsym && !novt &&
-		!( p -> variant & AVIRHIP_VARIANT_UP2_PLAIN_V ))
+	if( up2_vt( p, D ))
 	{
 		hipLaunchKernelGGL(( k_up2< U2_RB == 8, 0 > ), dim3( items ), dim3( U2_NT ),
 			ldspad, st, P );
