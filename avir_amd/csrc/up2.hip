@@ -39,6 +39,7 @@
 // order, interpolation sums started from +0.0f => bit-identical output.
 
 #include "plan.h"
+#include "up2_chunks.h"
 #include <algorithm>
 #include <string.h>
 #include <stdlib.h>
@@ -70,7 +71,9 @@ struct Up2Params
 	int rmin, rmax; // source rows that exist behind `src` (a window: plan.h)
 	float* dst; long dst_ss; int dst_row0; int nw, nh;
 	int srow_lo, srow_hi;
-	int nstrips, chunk0, nchunks, cq; // cq: source rows (output row pairs) per chunk
+	int nstrips, chunk0, nchunks;
+	int cq, nlong; // source rows (output row pairs) per chunk: the first nlong
+		// chunks of a strip hold cq + U2_RB, the others cq (up2_chunks.h)
 	// IO != 0: the caller's image instead of dst -- uint8 / uint16 (the output
 	// stage of dither(), avir.h:4392-4419, without bit-depth truncation) or
 	// float pixels of 1-3 channels; ibase = the band's first row
@@ -371,7 +374,8 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 		rm * ( qd + 1 ) + ( xcd - rm ) * qd ) + ( b >> 3 );
 
 	// strip-major: an XCD's contiguous item range holds whole strips, i.e.
-	// the same mix of full and short (last) chunks as every other XCD
+	// the same mix of long and short chunks as every other XCD; a strip's
+	// long chunks come first
 	const int strip = item / P.nchunks;
 	const int chunk = P.chunk0 + item - strip * P.nchunks;
 	const int tid = threadIdx.x;
@@ -379,8 +383,9 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 	const int col = tid >> 1; // column within the strip (vertical phase)
 
 	const int qx0 = strip * ( U2_TW / 2 );
-	const int qy0 = chunk * P.cq;
-	const int qy1 = min( qy0 + P.cq, P.nh >> 1 );
+	const int qy0 = up2_chunk_first( chunk, P.cq, P.nlong );
+	const int qy1 = min( qy0 + up2_chunk_rows( chunk, P.cq, P.nlong ),
+		P.nh >> 1 );
 	const int u0 = qy0 - 9;               // first Text row index consumed
 	const int nsteps = qy1 - qy0 + 18;    // 6 preload + 12 warm-up + rows
 	const int xo = qx0 * 2 + col;         // this thread's output column
@@ -1722,58 +1727,40 @@ int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 	P.istride_b = p -> new_w * p -> io_ch * ( io == 1 || io == 4 ? 1 :
 		( io == 2 || io == 5 ? 2 : 4 ));
 
-	// Chunk height. A chunk of cq source rows costs (cq + 18) / U2_RB marching
-	// steps (6 rows of preload + 12 of warm-up), so cq = U2_RB*k - 18 wastes
-	// nothing. The kernel is VALU-bound and a CU shares its VALUs among its
-	// resident workgroups (up to 8), so a launch whose items are all resident
-	// at once takes about
-	//     m * k / thr( m ),   m = ceil( items / 256 CUs )
-	// step-times -- the most loaded CU finishes last, and thr is the measured
-	// VALU throughput of a CU running m workgroups (cq sweeps of cfg2 and cfg3,
-	// profiles/r01_up2_chunk_sweep.txt). Few tall chunks waste little warm-up
-	// work, many short ones balance and fill the CUs; launches of more than
-	// 8 x 256 items run in partial rounds and measured ~6 % worse than their
-	// step count.
-	int cq = 0;
-	{
-		static const double thr[ 9 ] = { 1.0, 0.3, 0.57, 0.8, 0.9, 0.9, 0.9,
-			0.97, 1.0 };
-		const int rows = ( row1 - row0 + 1 ) / 2 + 1; // source rows of the band
-		double best = -1.0;
+	// Chunk heights (up2_chunks.h). A chunk of h source rows costs
+	// ( h + 18 ) / U2_RB marching steps (6 rows of preload + 12 of warm-up), so
+	// heights U2_RB * k - 18 waste nothing. The band's steps are dealt over n
+	// chunks as evenly as they go: the first nlong chunks of a strip are one
+	// step taller than the rest, none is left short. n is the count of the
+	// least modelled cost: the kernel is VALU-bound and a CU shares its VALUs
+	// among its resident workgroups (up to 8), so a launch whose items are all
+	// resident at once ends when its most loaded CU does (up2_split_cost; the
+	// fit: profiles/up2_chunks/). The split lies on the frame's grid (chunk 0
+	// starts at source row 0) whichever band is asked for.
+	const int rows = ( row1 - 1 ) / 2 - row0 / 2 + 1; // source rows of the band
+	Up2Split sp = up2_split_choose( rows, P.nstrips );
 
-		for( int k = 10; k <= 64; k++ )
-		{
-			const int c = U2_RB * k - 18;
-			const long nch = ( rows + c - 1 ) / c;
-			const long items = nch * P.nstrips;
-			const long m = ( items + 255 ) / 256;
-			const double cost = ( m <= 8 ? (double) m * k / thr[ m ] :
-				(double) items * k / 256.0 * 1.06 );
-
-			if( best < 0.0 || cost < best )
-			{
-				best = cost;
-				cq = c;
-			}
-
-			if( nch == 1 )
-			{
-				break;
-			}
-		}
-	}
-
+	// sweeps (tools/cq_sweep.sh, tools/up2_chunk_sweep.py): a uniform height,
+	// or the balanced split of a given chunk count
 	const char* ecq = getenv( "AVIRHIP_UP2_CQ" );
+	const char* enc = getenv( "AVIRHIP_UP2_NCHUNKS" );
 
 	if( ecq != nullptr && atoi( ecq ) >= 6 )
 	{
-		cq = (( atoi( ecq ) + 18 + U2_RB - 1 ) / U2_RB ) * U2_RB - 18;
+		sp.cq = (( atoi( ecq ) + 18 + U2_RB - 1 ) / U2_RB ) * U2_RB - 18;
+		sp.nlong = 0;
+	}
+	else
+	if( enc != nullptr && atoi( enc ) >= 1 &&
+		up2_split_n( rows, atoi( enc ), 4 ).n != 0 )
+	{
+		sp = up2_split_n( rows, atoi( enc ), 4 );
 	}
 
-	P.cq = cq;
-	const int cr = P.cq * 2;
-	P.chunk0 = row0 / cr;
-	const int chunk1 = ( row1 - 1 ) / cr;
+	P.cq = sp.cq;
+	P.nlong = sp.nlong;
+	P.chunk0 = up2_chunk_of( row0 / 2, P.cq, P.nlong );
+	const int chunk1 = up2_chunk_of(( row1 - 1 ) / 2, P.cq, P.nlong );
 
 	P.coef = D -> d_coef;
 #ifdef U2_DBG
@@ -1798,8 +1785,9 @@ int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 		int nb = -1;
 		(void) hipOccupancyMaxActiveBlocksPerMultiprocessor( &nb,
 			(const void*) k_up2< false, 0 >, U2_NT, 0 );
-		fprintf( stderr, "k_up2: %d items (strips %d, cq %d), occupancy API "
-			"%d workgroups/CU\n", items, P.nstrips, P.cq, nb );
+		fprintf( stderr, "k_up2: %d items (strips %d, cq %d, nlong %d), "
+			"occupancy API %d workgroups/CU\n", items, P.nstrips, P.cq,
+			P.nlong, nb );
 	}
 
 	const char* pad = getenv( "AVIRHIP_UP2_LDSPAD" ); // residency experiments
