@@ -2,6 +2,10 @@
 """Differential fuzz of the execution paths: random geometries, channel
 counts, element types and parameters; the automatic path, its row bands and
 every forcible fast path must equal the generic kernels (path 1) bit for bit.
+CImageResizer cases also draw a CImageResizerParams set (the default, the five
+presets, two custom sets of tests/param_cases.py) from a second random stream
+seeded by the case index, so the first stream's geometries, types and flags
+do not depend on it.
 With a third argument "ref" the generic kernels' result is also compared with
 the reference itself (oracle/_ref must be built; the test suite's checker).
 usage: fuzz_paths.py [cases] [seed] [ref]"""
@@ -20,6 +24,30 @@ if REF:
     from oracle import bind as rb
 bad = 0
 ran = {}
+
+# CImageResizerParams sets: None = CImageResizerParamsDef; the presets by the
+# library's own index; two custom sets (9-tap correction filter; 14-tap
+# interpolation bank) as one change from the default
+PSETS = ["def", "def", "def", "ulr", "lr", "low", "high", "ultra",
+         "corr8.2", "int22"]
+PNAMES = ("CorrFltAlpha", "CorrFltLen", "IntFltAlpha", "IntFltCutoff",
+          "IntFltLen", "LPFltAlpha", "LPFltBaseLen", "LPFltCutoffMult")
+
+
+def params_of(name):
+    """-> (CImageResizerParams or None, the reference's 8 values or None)"""
+    if name == "def":
+        return None, None
+    if name in avir_amd.CImageResizerParams.PRESETS:
+        P = avir_amd.CImageResizerParams(name)
+    else:
+        P = avir_amd.CImageResizerParams("def")
+        if name == "corr8.2":
+            P.CorrFltLen = 8.2
+        else:
+            P.IntFltLen = 22.0
+    return P, [getattr(P, n) for n in PNAMES]
+
 
 
 def make(sh, sw, ch, dt, seed):
@@ -84,6 +112,9 @@ for it in range(N):
         if rng.rand() < 0.2:
             v.ox, v.oy = float(rng.uniform(-1, 1)), float(rng.uniform(-1, 1))
     kstep = float(rng.choice([0.0, 0.0, 0.0, 1.7, 0.6])) if not lanc else 0.0
+    # (its own stream: `rng` draws what it drew before there were sets)
+    pname = PSETS[np.random.RandomState(1000003 + it).randint(0, len(PSETS))]
+    P, pvals = (None, None) if lanc else params_of(pname)
     # (path 58: the pass kernels of path 5 with AVIRHIP_VARIANT_UPG_TWO_PASS --
     # upsizing plans through FltBuf instead of the fused launch)
     # ... path 516: AVIRHIP_VARIANT_UPG_FUSED, the fused launch at any size)
@@ -101,7 +132,7 @@ for it in range(N):
                 p = r.plan(sw, sh, nw, nh, ch, lp, avir_amd._NP2T[np.dtype(tin)],
                            avir_amd._NP2T[np.dtype(tout)])
             else:
-                r = avir_amd.CImageResizer(bits)
+                r = avir_amd.CImageResizer(bits, 0, P)
                 p = r.plan(sw, sh, nw, nh, ch, kstep, v,
                            avir_amd._NP2T[np.dtype(tin)],
                            avir_amd._NP2T[np.dtype(tout)])
@@ -136,13 +167,13 @@ for it in range(N):
         else:
             want = rb.ref_avir(src, nw, nh, k=kstep, out_dtype=tout,
                                resbits=bits, ox=v.ox, oy=v.oy,
-                               build_mode=v.BuildMode,
+                               build_mode=v.BuildMode, params=pvals,
                                gamma=bool(v.UseSRGBGamma), alpha=v.AlphaIndex)
         if want.tobytes() != res[1].tobytes():
             print("REF MISMATCH", it, (sw, sh, nw, nh, ch, tin.__name__,
                                        tout.__name__, lanc, bits,
                                        v.UseSRGBGamma, v.AlphaIndex,
-                                       v.BuildMode, kstep))
+                                       v.BuildMode, kstep, pname))
             bad += 1
     if os.environ.get("FUZZ_DETAIL") and int(os.environ["FUZZ_DETAIL"]) == it:
         # where a case's paths differ from the generic kernels (debugging aid)
@@ -162,7 +193,7 @@ for it in range(N):
             print("MISMATCH", it, (sw, sh, nw, nh, ch, tin.__name__,
                                    tout.__name__, "lancir" if lanc else bits,
                                    v.UseSRGBGamma, v.AlphaIndex, v.BuildMode,
-                                   kstep),
+                                   kstep, pname),
                   "path", path, "differs in",
                   int((got != res[1]).sum()), "elements")
             bad += 1
