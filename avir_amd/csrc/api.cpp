@@ -1316,6 +1316,54 @@ namespace avirhip {
 
 static int clone_plan( const avirhip_plan* s, int device, avirhip_plan** out );
 
+// The copy streams and the 2 * nb + 1 events of the band pipeline, made when a
+// plan's first pipelined call needs them: built aside and committed to the
+// plan only when complete -- a plan must never hold half a set (the next call
+// would index past pipe_ev). false: they could not be made.
+static bool ensure_pipe_set( avirhip_plan* p, const int nb )
+{
+	if( p -> pipe_in != nullptr )
+	{
+		return( true );
+	}
+
+	hipStream_t a = nullptr, b = nullptr;
+	std::vector< hipEvent_t > evs;
+	bool ok = ( hipStreamCreateWithFlags( &a, hipStreamNonBlocking ) ==
+		hipSuccess );
+
+	ok = ok && ( hipStreamCreateWithFlags( &b, hipStreamNonBlocking ) ==
+		hipSuccess );
+
+	for( int i = 0; ok && i < 2 * nb + 1; i++ )
+	{
+		hipEvent_t e;
+		ok = ( hipEventCreateWithFlags( &e, hipEventDisableTiming ) ==
+			hipSuccess );
+
+		if( ok ) evs.push_back( e );
+	}
+
+	if( !ok )
+	{
+		(void) hipGetLastError();
+
+		for( size_t i = 0; i < evs.size(); i++ )
+		{
+			(void) hipEventDestroy( evs[ i ]);
+		}
+
+		if( a != nullptr ) (void) hipStreamDestroy( a );
+		if( b != nullptr ) (void) hipStreamDestroy( b );
+
+		return( false );
+	}
+
+	p -> pipe_in = a; p -> pipe_out = b;
+	p -> pipe_ev.swap( evs );
+	return( true );
+}
+
 // Host-pointer call, pipelined (the call every existing caller of the
 // reference makes, avir.h:4680-4684): the frame in row bands, the source rows
 // of band b + 1 travelling host -> device (an uploader thread: a copy from
@@ -1350,44 +1398,9 @@ static int exec_host_pipelined( avirhip_plan* p, const void* src, void* dst,
 		return( 1 );
 	}
 
-	if( p -> pipe_in == nullptr )
+	if( !ensure_pipe_set( p, NB ))
 	{
-		// built aside and committed to the plan only when complete: a plan
-		// must never hold half a set (the next call would index past pipe_ev)
-		hipStream_t a = nullptr, b = nullptr;
-		std::vector< hipEvent_t > evs;
-		bool ok = ( hipStreamCreateWithFlags( &a, hipStreamNonBlocking ) ==
-			hipSuccess );
-
-		ok = ok && ( hipStreamCreateWithFlags( &b, hipStreamNonBlocking ) ==
-			hipSuccess );
-
-		for( int i = 0; ok && i < 2 * NB + 1; i++ )
-		{
-			hipEvent_t e;
-			ok = ( hipEventCreateWithFlags( &e, hipEventDisableTiming ) ==
-				hipSuccess );
-
-			if( ok ) evs.push_back( e );
-		}
-
-		if( !ok )
-		{
-			(void) hipGetLastError();
-
-			for( size_t i = 0; i < evs.size(); i++ )
-			{
-				(void) hipEventDestroy( evs[ i ]);
-			}
-
-			if( a != nullptr ) (void) hipStreamDestroy( a );
-			if( b != nullptr ) (void) hipStreamDestroy( b );
-
-			return( 1 ); // (the serial path needs none of this)
-		}
-
-		p -> pipe_in = a; p -> pipe_out = b;
-		p -> pipe_ev.swap( evs );
+		return( 1 ); // (the serial path needs none of this)
 	}
 
 	hipStream_t s_in = (hipStream_t) p -> pipe_in;
@@ -1582,14 +1595,47 @@ static int exec_host_pipelined( avirhip_plan* p, const void* src, void* dst,
 }
 
 
-// `win_rows` > 0: `src` holds only the source rows [win_first, win_first +
-// win_rows) of the frame (avirhip_resize_window); otherwise the whole frame.
-static int exec_any( avirhip_plan* p, const void* src, int src_mem, void* dst,
-	int dst_mem, int row0, int row1, void* stream, bool have_lock = false,
-	int win_first = 0, int win_rows = 0 )
+// ---- the execute entry: every whole-frame, band, window, sharded and timed
+// call is one exec_any, which is a sequence of the stages below
+
+// bytes behind an image of `rows` rows at a pitch of `stride` elements: the
+// last row ends with its last pixel
+static size_t image_bytes( int rows, long stride, int w, int ch, int type )
 {
-	src_mem = avirhip_resolve_mem( src, src_mem );
-	dst_mem = avirhip_resolve_mem( dst, dst_mem );
+	return(( (size_t) ( rows - 1 ) * stride + (size_t) w * ch ) *
+		dtype_size( type ));
+}
+
+static bool share_bytes( const void* a, size_t na, const void* b, size_t nb )
+{
+	return( (const char*) a < (const char*) b + nb &&
+		(const char*) b < (const char*) a + na );
+}
+
+// The caller's current device, put back on every way out. `want` >= 0: a
+// plan's tables and scratch live on the device it was created on -- the call
+// runs there, whatever device the calling thread has current (and the caller's
+// device is put back only if it was left).
+struct DeviceGuard
+{
+	int keep;
+	bool on;
+	explicit DeviceGuard( int want = -1 ) : keep( 0 ), on( want < 0 )
+	{
+		if( hipGetDevice( &keep ) == hipSuccess && want >= 0 && keep != want )
+		{
+			on = ( hipSetDevice( want ) == hipSuccess );
+		}
+	}
+	~DeviceGuard() { if( on ) (void) hipSetDevice( keep ); }
+};
+
+// The argument, window and band checks of a call. `nothing`: the call is valid
+// and has no row to compute.
+static int check_call( const avirhip_plan* p, const void* src, const void* dst,
+	int row0, int row1, int win_first, int win_rows, bool& nothing )
+{
+	nothing = false;
 
 	if( p == nullptr || src == nullptr || dst == nullptr || row0 < 0 ||
 		row1 > p -> new_h || row0 > row1 )
@@ -1598,9 +1644,7 @@ static int exec_any( avirhip_plan* p, const void* src, int src_mem, void* dst,
 		return( AVIRHIP_EINVAL );
 	}
 
-	const bool windowed = ( win_rows > 0 );
-
-	if( windowed )
+	if( win_rows > 0 )
 	{
 		int need_a = 0, need_b = -1;
 		band_src_rows( p, row0, row1, &need_a, &need_b );
@@ -1621,6 +1665,7 @@ static int exec_any( avirhip_plan* p, const void* src, int src_mem, void* dst,
 		// of the window is made
 		if( row1 <= row0 )
 		{
+			nothing = true;
 			return( AVIRHIP_OK );
 		}
 	}
@@ -1633,205 +1678,203 @@ static int exec_any( avirhip_plan* p, const void* src, int src_mem, void* dst,
 		return( AVIRHIP_EUNSUPPORTED );
 	}
 
-	hipStream_t st = (hipStream_t) stream;
+	return( AVIRHIP_OK );
+}
 
-	// A plan's tables and scratch live on the device it was created on: run
-	// there, whatever device the calling thread has current, and put the
-	// caller's device back on every way out.
-	struct DeviceGuard
+// The plan a scratch-using call runs on, its lock in `held` (released on every
+// way out of the caller, a throw included). Scratch users take the plan's lock.
+// When another thread holds it (the reference allows concurrent resizeImage()
+// calls on one object, README.md:83-85), the call runs on a spare replica of
+// the plan instead -- same tables, its own scratch, staging buffers and last_*
+// state -- so that the two calls overlap on their streams rather than queue
+// behind one buffer set. Up to three spares; beyond that callers wait.
+static avirhip_plan* scratch_owner( avirhip_plan* p,
+	std::unique_lock< std::mutex >& held )
+{
+	held = std::unique_lock< std::mutex >( p -> exec_mtx, std::try_to_lock );
+
+	if( held.owns_lock() )
 	{
-		int keep;
-		bool on;
-		DeviceGuard( int want ) : keep( 0 ), on( false )
-		{
-			if( hipGetDevice( &keep ) == hipSuccess && keep != want )
-			{
-				on = ( hipSetDevice( want ) == hipSuccess );
-			}
-		}
-		~DeviceGuard() { if( on ) (void) hipSetDevice( keep ); }
-	} devguard( p -> device );
-
-	// Calls on one plan share its scratch buffers: serialise them (the
-	// reference allows concurrent resizeImage() calls on one object). The
-	// only scratch-free case, device-resident float RGBA through the
-	// single-launch 2x kernels, skips this.
-	const size_t src_bytes = ( (size_t) ( p -> src_h - 1 ) * p -> src_stride +
-		(size_t) p -> src_w * p -> io_ch ) * dtype_size( p -> in_type );
-	// (what `src` addresses: the frame, or the rows of a window)
-	const size_t win_bytes = ( !windowed ? src_bytes :
-		( (size_t) ( win_rows - 1 ) * p -> src_stride +
-		(size_t) p -> src_w * p -> io_ch ) * dtype_size( p -> in_type ));
-	const size_t row_bytes = (size_t) p -> new_stride *
-		dtype_size( p -> out_type );
-	const size_t dst_bytes = ( row1 > row0 ?
-		(size_t) ( row1 - row0 - 1 ) * row_bytes + (size_t) p -> new_w *
-		p -> io_ch * dtype_size( p -> out_type ) : 0 );
-	// (device buffers that share bytes: [src, src + win_bytes) is what `src`
-	// addresses, a window's rows included)
-	const bool shared = ( src_mem == AVIRHIP_MEM_DEVICE &&
-		dst_mem == AVIRHIP_MEM_DEVICE &&
-		(const char*) src < (const char*) dst + dst_bytes &&
-		(const char*) dst < (const char*) src + win_bytes );
-	const bool overlap = ( !windowed && shared );
-	// a window that overlaps its destination band: a staged window is copied
-	// before anything is stored; a native one would be read where it lies while
-	// the band is written -- it is copied aside first, like a host window
-	const bool win_aside = ( windowed && ( shared ||
-		src_mem == AVIRHIP_MEM_HOST ));
-
-	const int xpath = ( p -> path != 0 ? p -> path : p -> auto_path );
-	// (CLancIR is not thread-safe in the reference either, lancir.h:319-349:
-	// its plans always take the lock, and may allocate scratch under it)
-	const bool scratch_free = ( !p -> is_lancir && !overlap && !windowed &&
-		xpath == 4 &&
-		p -> in_type == AVIRHIP_F32 &&
-		p -> out_type == AVIRHIP_F32 && p -> ch == p -> io_ch &&
-		!p -> gamma && src_mem == AVIRHIP_MEM_DEVICE &&
-		dst_mem == AVIRHIP_MEM_DEVICE &&
-		// ... and only when the 2x kernel cannot refuse the call and fall
-		// back to the generic kernels (which use scratch)
-		(( (uintptr_t) src | (uintptr_t) dst ) & 15 ) == 0 &&
-		( p -> src_stride & 3 ) == 0 &&
-		(long) p -> src_stride * 4 < ( 1L << 22 ) &&
-		(long) p -> new_w * 16 < ( 1L << 22 ));
-
-	// Scratch users take the plan's lock. When another thread holds it (the
-	// reference allows concurrent resizeImage() calls on one object,
-	// README.md:83-85), the call runs on a spare replica of the plan instead
-	// -- same tables, its own scratch -- so that the two calls overlap on
-	// their streams rather than queue behind one buffer set. Up to three
-	// spares; beyond that callers wait.
-	std::unique_lock< std::mutex > guard( p -> exec_mtx, std::defer_lock );
-
-	if( !scratch_free && !have_lock && !guard.try_lock())
-	{
-		avirhip_plan* spare = nullptr;
-		{
-			// (its own mutex: avirhip_resize_sharded holds shard_mtx for the
-			// whole call and reaches this point for the band on the plan's
-			// own device)
-			std::lock_guard< std::mutex > sl( p -> spare_mtx );
-
-			for( size_t i = 0; i < p -> spares.size() && spare == nullptr; i++ )
-			{
-				if( p -> spares[ i ] -> exec_mtx.try_lock())
-				{
-					spare = p -> spares[ i ];
-				}
-			}
-
-			if( spare == nullptr && p -> spares.size() < 3 && !p -> is_spare )
-			{
-				if( clone_plan( p, p -> device, &spare ) == AVIRHIP_OK )
-				{
-					spare -> is_spare = 1;
-					spare -> exec_mtx.lock();
-					p -> spares.push_back( spare );
-				}
-				else
-				{
-					spare = nullptr;
-				}
-			}
-		}
-
-		if( spare != nullptr )
-		{
-			// (exec_any on the spare: its mutex is held by this thread, and
-			// released on every way out -- a throw included)
-			std::unique_lock< std::mutex > sg( spare -> exec_mtx,
-				std::adopt_lock );
-
-			return( exec_any( spare, src, src_mem, dst, dst_mem, row0, row1,
-				stream, true, win_first, win_rows ));
-		}
-
-		guard.lock();
+		return( p );
 	}
 
-	// hipStreamPerThread is ONE handle that names a different stream in every
-	// thread: such a call records the plan's event itself, when it ends (below).
-	struct PerThreadRecord
+	avirhip_plan* spare = nullptr;
 	{
-		avirhip_plan* p;
-		hipStream_t st;
-		bool on;
-		~PerThreadRecord()
+		// (its own mutex: avirhip_resize_sharded holds shard_mtx for the
+		// whole call and reaches this point for the band on the plan's
+		// own device)
+		std::lock_guard< std::mutex > sl( p -> spare_mtx );
+
+		for( size_t i = 0; i < p -> spares.size() && spare == nullptr; i++ )
 		{
-			if( on && ( p -> last_done == nullptr ||
-				hipEventRecord( p -> last_done, st ) != hipSuccess ))
+			if( p -> spares[ i ] -> exec_mtx.try_lock())
 			{
-				(void) hipGetLastError();
-				(void) hipStreamSynchronize( st );
+				spare = p -> spares[ i ];
 			}
 		}
-	} ptrec = { p, st, false };
 
-	if( !scratch_free )
-	{
-		// The plan's scratch buffers are reused by the next call. Calls on one
-		// stream are ordered by the stream itself; only when the stream
-		// CHANGES does the new one have to wait for what the old one still
-		// holds -- the event is recorded on the old stream then, not after
-		// every call: a record between two frames is a barrier packet with a
-		// release fence, 6-8 us of idle GPU per frame (the kernel trace of
-		// 640x480 -> 1024x768: H -> V inside a call 0.6 us apart, V -> the next
-		// call's H 7.7 us). "The same stream" is the same handle AND, for
-		// hipStreamPerThread, the same thread. (hipStreamGetId would also tell a
-		// destroyed stream's recycled handle value apart, but it is a hip_7.1
-		// symbol: the runtime PyTorch ships is 7.0 and could not load the
-		// library. A caller that destroys a stream with calls of this plan
-		// still in flight has to synchronise it first.)
-		const bool per_thread = ( st == hipStreamPerThread );
-		const std::thread::id tid = std::this_thread::get_id();
-
-		if( p -> last_used )
+		if( spare == nullptr && p -> spares.size() < 3 && !p -> is_spare )
 		{
-			if( p -> last_done == nullptr )
+			if( clone_plan( p, p -> device, &spare ) == AVIRHIP_OK )
 			{
-				AVIRHIP_HIPCHECK( hipEventCreateWithFlags( &p -> last_done,
-					hipEventDisableTiming ));
-			}
-
-			if( p -> last_recorded )
-			{
-				// (the last call was on a per-thread stream and recorded the
-				// event when it ended)
-				if( !( per_thread && p -> last_tid == tid ))
-				{
-					AVIRHIP_HIPCHECK( hipStreamWaitEvent( st, p -> last_done, 0 ));
-				}
+				spare -> is_spare = 1;
+				spare -> exec_mtx.lock();
+				p -> spares.push_back( spare );
 			}
 			else
-			if( p -> last_stream != (void*) st )
 			{
-				if( hipEventRecord( p -> last_done,
-					(hipStream_t) p -> last_stream ) != hipSuccess ||
-					hipStreamWaitEvent( st, p -> last_done, 0 ) != hipSuccess )
-				{
-					// (the old stream is gone: what it held may still run)
-					(void) hipGetLastError();
-					AVIRHIP_HIPCHECK( hipDeviceSynchronize() );
-				}
+				spare = nullptr;
 			}
 		}
-		else
-		if( per_thread && p -> last_done == nullptr )
+	}
+
+	if( spare != nullptr )
+	{
+		held = std::unique_lock< std::mutex >( spare -> exec_mtx,
+			std::adopt_lock );
+		return( spare );
+	}
+
+	held.lock();
+	return( p );
+}
+
+// hipStreamPerThread is ONE handle that names a different stream in every
+// thread: such a call records the plan's event itself, when it ends.
+struct PerThreadRecord
+{
+	avirhip_plan* p;
+	hipStream_t st;
+	bool on;
+	~PerThreadRecord()
+	{
+		if( on && ( p -> last_done == nullptr ||
+			hipEventRecord( p -> last_done, st ) != hipSuccess ))
+		{
+			(void) hipGetLastError();
+			(void) hipStreamSynchronize( st );
+		}
+	}
+};
+
+// The plan's scratch buffers are reused by the next call. Calls on one
+// stream are ordered by the stream itself; only when the stream
+// CHANGES does the new one have to wait for what the old one still
+// holds -- the event is recorded on the old stream then, not after
+// every call: a record between two frames is a barrier packet with a
+// release fence, 6-8 us of idle GPU per frame (the kernel trace of
+// 640x480 -> 1024x768: H -> V inside a call 0.6 us apart, V -> the next
+// call's H 7.7 us). "The same stream" is the same handle AND, for
+// hipStreamPerThread, the same thread. (hipStreamGetId would also tell a
+// destroyed stream's recycled handle value apart, but it is a hip_7.1
+// symbol: the runtime PyTorch ships is 7.0 and could not load the
+// library. A caller that destroys a stream with calls of this plan
+// still in flight has to synchronise it first.)
+// `record_at_end`: the caller's PerThreadRecord is armed.
+static int order_behind_last_call( avirhip_plan* p, hipStream_t st,
+	bool& record_at_end )
+{
+	const bool per_thread = ( st == hipStreamPerThread );
+	const std::thread::id tid = std::this_thread::get_id();
+
+	if( p -> last_used )
+	{
+		if( p -> last_done == nullptr )
 		{
 			AVIRHIP_HIPCHECK( hipEventCreateWithFlags( &p -> last_done,
 				hipEventDisableTiming ));
 		}
 
-		p -> last_stream = (void*) st;
-		p -> last_tid = tid;
-		p -> last_recorded = per_thread;
-		p -> last_used = true;
-		ptrec.on = per_thread;
+		if( p -> last_recorded )
+		{
+			// (the last call was on a per-thread stream and recorded the
+			// event when it ended)
+			if( !( per_thread && p -> last_tid == tid ))
+			{
+				AVIRHIP_HIPCHECK( hipStreamWaitEvent( st, p -> last_done, 0 ));
+			}
+		}
+		else
+		if( p -> last_stream != (void*) st )
+		{
+			if( hipEventRecord( p -> last_done,
+				(hipStream_t) p -> last_stream ) != hipSuccess ||
+				hipStreamWaitEvent( st, p -> last_done, 0 ) != hipSuccess )
+			{
+				// (the old stream is gone: what it held may still run)
+				(void) hipGetLastError();
+				AVIRHIP_HIPCHECK( hipDeviceSynchronize() );
+			}
+		}
+	}
+	else
+	if( per_thread && p -> last_done == nullptr )
+	{
+		AVIRHIP_HIPCHECK( hipEventCreateWithFlags( &p -> last_done,
+			hipEventDisableTiming ));
 	}
 
-	const void* dsrc = src;
-	void* ddst = dst;
+	p -> last_stream = (void*) st;
+	p -> last_tid = tid;
+	p -> last_recorded = per_thread;
+	p -> last_used = true;
+	record_at_end = per_thread;
+	return( AVIRHIP_OK );
+}
+
+// Where the kernels of one call read the source from, and which bytes move
+// before they do:
+//   call                                      stage_src  copy            kernels read     window
+//   device frame, no bytes shared with dst    --         --              src              --
+//   device frame sharing bytes with dst       frame      frame, D2D      stage            --
+//   host frame                                frame      frame, H2D, late  stage          --
+//   window, marching kernel, device, apart    --         --              src - win_off    yes
+//   window, marching kernel, host or shared   window     window to 0     stage - win_off  yes
+//   window, any other plan                    frame      window to win_off  stage         --
+struct SrcRoute
+{
+	size_t stage_bytes; // what stage_src has to hold (0: `src` is read where it lies)
+	size_t copy_bytes;  // bytes of `src` copied there (0: none) ...
+	size_t copy_at;     // ... to this offset of stage_src ...
+	hipMemcpyKind kind;
+	bool late;          // ... only after the band pipeline has declined the call
+	size_t base_off;    // subtracted from the buffer: the virtual frame base
+	SrcWindow win;      // the kernels' row clamp: an argument of this call
+};
+
+static SrcRoute src_route( const avirhip_plan* p, const void* src, int src_mem,
+	const void* dst, int dst_mem, int row0, int row1, int win_first,
+	int win_rows )
+{
+	const bool windowed = ( win_rows > 0 );
+	const bool host = ( src_mem == AVIRHIP_MEM_HOST );
+	const size_t src_bytes = image_bytes( p -> src_h, p -> src_stride,
+		p -> src_w, p -> io_ch, p -> in_type );
+	// (what `src` addresses: the frame, or the rows of a window)
+	const size_t win_bytes = ( !windowed ? src_bytes : image_bytes( win_rows,
+		p -> src_stride, p -> src_w, p -> io_ch, p -> in_type ));
+	const size_t dst_bytes = ( row1 > row0 ? image_bytes( row1 - row0,
+		p -> new_stride, p -> new_w, p -> io_ch, p -> out_type ) : 0 );
+	const bool shared = ( src_mem == AVIRHIP_MEM_DEVICE &&
+		dst_mem == AVIRHIP_MEM_DEVICE &&
+		share_bytes( src, win_bytes, dst, dst_bytes ));
+	SrcRoute r = { 0, 0, 0, ( host ? hipMemcpyHostToDevice :
+		hipMemcpyDeviceToDevice ), false, 0, { 0, 0 }};
+
+	if( !windowed )
+	{
+		// NewBuf may alias SrcBuf (avir.h:4650-4652: allowed when the result is
+		// not larger). The reference survives that because it has consumed the
+		// source into FltBuf before it writes; the kernels here read the source
+		// while they write, so an overlapping device source is copied aside first.
+		if( host || shared )
+		{
+			r.stage_bytes = r.copy_bytes = src_bytes;
+			r.late = host;
+		}
+
+		return( r );
+	}
 
 	// A window on the marching kernels (exact-2x float RGBA plans: the sharded
 	// configurations of BASELINE.json): the kernels take a VIRTUAL frame base,
@@ -1840,104 +1883,160 @@ static int exec_any( avirhip_plan* p, const void* src, int src_mem, void* dst,
 	// frame" (a needed row outside the frame is the frame's first / last row,
 	// which avirhip_band_source_rows then names, so the window holds it). No
 	// frame-sized buffer: a device window is read where it lies (zero copy), a
-	// host window is uploaded into a window-sized staging buffer.
+	// host window is uploaded into a window-sized staging buffer -- and so is a
+	// device window that overlaps its destination band, which would otherwise be
+	// read where it lies while the band is written.
 	const size_t win_off = (size_t) win_first * p -> src_stride *
 		dtype_size( p -> in_type );
-	const bool dst_direct = ( dst_mem == AVIRHIP_MEM_DEVICE );
-	bool win_native = false;
+	const bool aside = ( host || shared );
+	bool native = false;
 
-	if( windowed && getenv( "AVIRHIP_NO_NATIVE_WINDOW" ) == nullptr )
+	if( getenv( "AVIRHIP_NO_NATIVE_WINDOW" ) == nullptr )
 	{
 		// (alignment of the pointers the kernel will see: the staging buffers
 		// are 256-byte aligned, win_off is a multiple of the row pitch)
-		const void* const vsrc = (const char*) ( !win_aside ?
+		const void* const vsrc = (const char*) ( !aside ?
 			src : (const void*) (uintptr_t) 256 ) - ( win_off & 255 );
-		const void* const vdst = ( dst_direct ? dst : (void*) (uintptr_t) 256 );
+		const void* const vdst = ( dst_mem == AVIRHIP_MEM_DEVICE ? dst :
+			(const void*) (uintptr_t) 256 );
+		const int xpath = ( p -> path != 0 ? p -> path : p -> auto_path );
 
-		win_native = ( xpath == 4 && ( p -> is_lancir ?
+		native = ( xpath == 4 && ( p -> is_lancir ?
 			lanc2_takes_window( p, vsrc, vdst ) :
 			up2_takes_window( p, vsrc, vdst )));
 	}
 
-	// (the kernels' row clamp: an argument of this call, never the plan's)
-	SrcWindow kwin = { 0, 0 };
-
-	if( src_mem == AVIRHIP_MEM_HOST || ( windowed && ( !win_native ||
-		win_aside )))
+	if( native )
 	{
-		const size_t need = ( win_native ? win_bytes : src_bytes );
-
-		const int rc = grow( p, &p -> stage_src, &p -> stage_src_bytes, need );
-		if( rc != 0 ) return( rc );
-
-		dsrc = p -> stage_src;
-	}
-
-	if( windowed && win_native )
-	{
-		if( win_aside )
-		{
-			AVIRHIP_HIPCHECK( hipMemcpyAsync( p -> stage_src, src, win_bytes,
-				( src_mem == AVIRHIP_MEM_HOST ? hipMemcpyHostToDevice :
-				hipMemcpyDeviceToDevice ), st ));
-		}
-
 		// (pointer arithmetic only: nothing below row win_first is ever read)
-		dsrc = (const void*) ( (uintptr_t) dsrc - win_off );
-		kwin.first = win_first;
-		kwin.rows = win_rows;
+		r.stage_bytes = r.copy_bytes = ( aside ? win_bytes : 0 );
+		r.base_off = win_off;
+		r.win.first = win_first;
+		r.win.rows = win_rows;
 	}
 	else
-	if( windowed )
 	{
 		// Other plans: the window's rows go to their place in a frame-sized
 		// staging buffer of the plan -- the only source bytes that move (SURVEY.md
 		// 8e: "GPU g receives source rows [r0 - halo, r1 + halo]"); the kernels
 		// then run as on a whole frame, and whatever they load outside the window
 		// never reaches a result (avirhip_band_source_rows).
-		AVIRHIP_HIPCHECK( hipMemcpyAsync( (char*) p -> stage_src + win_off,
-			src, win_bytes, ( src_mem == AVIRHIP_MEM_HOST ?
-			hipMemcpyHostToDevice : hipMemcpyDeviceToDevice ), st ));
+		r.stage_bytes = src_bytes;
+		r.copy_bytes = win_bytes;
+		r.copy_at = win_off;
 	}
 
-	// NewBuf may alias SrcBuf (avir.h:4650-4652: allowed when the result is
-	// not larger). The reference survives that because it has consumed the
-	// source into FltBuf before it writes; the kernels here read the source
-	// while they write, so an overlapping device source is copied aside first.
-	if( overlap )
+	return( r );
+}
+
+// the source copy of a route, if it has one
+static hipError_t copy_source( avirhip_plan* p, const SrcRoute& r,
+	const void* src, hipStream_t st )
+{
+	return( r.copy_bytes == 0 ? hipSuccess : hipMemcpyAsync(
+		(char*) p -> stage_src + r.copy_at, src, r.copy_bytes, r.kind, st ));
+}
+
+// Performs a route up to the pointer the kernels read, `*dsrc`: grows the
+// staging buffer, issues the copy unless it is a late one.
+static int stage_source( avirhip_plan* p, const SrcRoute& r, const void* src,
+	hipStream_t st, const void** dsrc )
+{
+	const int rc = grow( p, &p -> stage_src, &p -> stage_src_bytes,
+		r.stage_bytes );
+	if( rc != 0 ) return( rc );
+
+	if( !r.late )
 	{
-		const int rc = grow( p, &p -> stage_src, &p -> stage_src_bytes,
-			src_bytes );
+		AVIRHIP_HIPCHECK( copy_source( p, r, src, st ));
+	}
+
+	*dsrc = (const void*) ( (uintptr_t) ( r.stage_bytes != 0 ?
+		p -> stage_src : src ) - r.base_off );
+	return( AVIRHIP_OK );
+}
+
+// `win_rows` > 0: `src` holds only the source rows [win_first, win_first +
+// win_rows) of the frame (avirhip_resize_window); otherwise the whole frame.
+static int exec_any( avirhip_plan* p, const void* src, int src_mem, void* dst,
+	int dst_mem, int row0, int row1, void* stream, int win_first = 0,
+	int win_rows = 0 )
+{
+	src_mem = avirhip_resolve_mem( src, src_mem );
+	dst_mem = avirhip_resolve_mem( dst, dst_mem );
+	bool nothing;
+	int rc = check_call( p, src, dst, row0, row1, win_first, win_rows, nothing );
+
+	if( rc != 0 || nothing )
+	{
+		return( rc );
+	}
+
+	hipStream_t st = (hipStream_t) stream;
+	DeviceGuard devguard( p -> device );
+	const bool windowed = ( win_rows > 0 );
+	const bool host_src = ( src_mem == AVIRHIP_MEM_HOST );
+	const bool host_dst = ( dst_mem == AVIRHIP_MEM_HOST );
+	const size_t src_bytes = image_bytes( p -> src_h, p -> src_stride,
+		p -> src_w, p -> io_ch, p -> in_type );
+	const size_t row_bytes = (size_t) p -> new_stride *
+		dtype_size( p -> out_type );
+	const size_t payload = (size_t) p -> new_w * p -> io_ch *
+		dtype_size( p -> out_type );
+	const size_t dst_bytes = ( row1 > row0 ?
+		(size_t) ( row1 - row0 - 1 ) * row_bytes + payload : 0 );
+	// (NewBuf may alias SrcBuf, avir.h:4650-4652)
+	const bool alias = ( !windowed &&
+		share_bytes( src, src_bytes, dst, dst_bytes ));
+
+	// Calls on one plan share its scratch buffers: serialise them (the
+	// reference allows concurrent resizeImage() calls on one object). The
+	// only scratch-free case, device-resident float RGBA through the
+	// single-launch 2x kernel, skips this -- when that kernel cannot refuse the
+	// call and fall back to the generic kernels (which use scratch).
+	// (CLancIR is not thread-safe in the reference either, lancir.h:319-349:
+	// its plans always take the lock, and may allocate scratch under it)
+	const bool scratch_free = ( !p -> is_lancir && !windowed && !alias &&
+		( p -> path != 0 ? p -> path : p -> auto_path ) == 4 &&
+		src_mem == AVIRHIP_MEM_DEVICE && dst_mem == AVIRHIP_MEM_DEVICE &&
+		// (stricter than the kernel, which stores 8-byte pieces: kept, so that
+		// no call moves between the locked and the lock-free route)
+		( (uintptr_t) dst & 15 ) == 0 &&
+		up2_takes_window( p, src, dst ));
+
+	std::unique_lock< std::mutex > held;
+	avirhip_plan* const q = ( scratch_free ? p : scratch_owner( p, held ));
+	PerThreadRecord ptrec = { q, st, false };
+
+	if( !scratch_free )
+	{
+		rc = order_behind_last_call( q, st, ptrec.on );
+		if( rc != 0 ) return( rc );
+	}
+
+	const SrcRoute route = src_route( q, src, src_mem, dst, dst_mem, row0, row1,
+		win_first, win_rows );
+	const void* dsrc;
+	void* ddst = dst;
+
+	rc = stage_source( q, route, src, st, &dsrc );
+	if( rc != 0 ) return( rc );
+
+	if( host_dst )
+	{
+		rc = grow( q, &q -> stage_dst, &q -> stage_dst_bytes, dst_bytes );
 		if( rc != 0 ) return( rc );
 
-		AVIRHIP_HIPCHECK( hipMemcpyAsync( p -> stage_src, src, src_bytes,
-			hipMemcpyDeviceToDevice, st ));
-		dsrc = p -> stage_src;
+		ddst = q -> stage_dst;
 	}
 
-	if( dst_mem == AVIRHIP_MEM_HOST )
+	// (an aliasing call: result rows copied down while source rows still travel
+	// up would overwrite them -- such calls keep the serial order, whole source
+	// up first)
+	if( host_src && host_dst && !windowed && !alias && row0 == 0 &&
+		row1 == q -> new_h && payload == row_bytes )
 	{
-		const int rc = grow( p, &p -> stage_dst, &p -> stage_dst_bytes,
-			dst_bytes );
-		if( rc != 0 ) return( rc );
-
-		ddst = p -> stage_dst;
-	}
-
-	int rc = 1;
-
-	// (NewBuf may alias SrcBuf, avir.h:4650-4652: result rows copied down while
-	// source rows still travel up would overwrite them -- such calls keep the
-	// serial order, whole source up first)
-	const bool host_alias = ( (const char*) src < (const char*) dst + dst_bytes &&
-		(const char*) dst < (const char*) src + src_bytes );
-
-	if( src_mem == AVIRHIP_MEM_HOST && dst_mem == AVIRHIP_MEM_HOST &&
-		!windowed && !host_alias && row0 == 0 && row1 == p -> new_h &&
-		(size_t) p -> new_w * p -> io_ch * dtype_size( p -> out_type ) ==
-		row_bytes )
-	{
-		rc = exec_host_pipelined( p, src, dst, src_bytes, dst_bytes, row_bytes,
+		rc = exec_host_pipelined( q, src, dst, src_bytes, dst_bytes, row_bytes,
 			st );
 
 		if( rc != 1 )
@@ -1946,20 +2045,16 @@ static int exec_any( avirhip_plan* p, const void* src, int src_mem, void* dst,
 		}
 	}
 
-	if( src_mem == AVIRHIP_MEM_HOST && !windowed )
+	if( route.late )
 	{
-		AVIRHIP_HIPCHECK( hipMemcpyAsync( p -> stage_src, src, src_bytes,
-			hipMemcpyHostToDevice, st ));
+		AVIRHIP_HIPCHECK( copy_source( q, route, src, st ));
 	}
 
-	rc = exec_device( p, dsrc, ddst, row0, row1, st, kwin );
+	rc = exec_device( q, dsrc, ddst, row0, row1, st, route.win );
 	if( rc != 0 ) return( rc );
 
-	if( dst_mem == AVIRHIP_MEM_HOST )
+	if( host_dst )
 	{
-		const size_t payload = (size_t) p -> new_w * p -> io_ch *
-			dtype_size( p -> out_type );
-
 		if( payload == row_bytes || row1 - row0 < 2 )
 		{
 			AVIRHIP_HIPCHECK( hipMemcpyAsync( dst, ddst, dst_bytes,
@@ -1977,7 +2072,7 @@ static int exec_any( avirhip_plan* p, const void* src, int src_mem, void* dst,
 		AVIRHIP_HIPCHECK( hipStreamSynchronize( st ));
 	}
 	else
-	if( src_mem == AVIRHIP_MEM_HOST )
+	if( host_src )
 	{
 		AVIRHIP_HIPCHECK( hipStreamSynchronize( st ));
 	}
@@ -2511,22 +2606,16 @@ try
 	const bool force_staged =
 		( getenv( "AVIRHIP_SHARDED_STAGED" ) != nullptr );
 
-	const size_t esz_in = dtype_size( p -> in_type );
 	const size_t esz_out = dtype_size( p -> out_type );
-	const size_t src_bytes = ( (size_t) ( p -> src_h - 1 ) * p -> src_stride +
-		(size_t) p -> src_w * p -> io_ch ) * esz_in;
+	const size_t src_bytes = image_bytes( p -> src_h, p -> src_stride,
+		p -> src_w, p -> io_ch, p -> in_type );
 	const size_t row_bytes = (size_t) p -> new_stride * esz_out;
 
 	// the replica list and the per-replica band / source buffers are shared
 	// by every sharded call on this plan; the caller's current device comes
 	// back on every way out
 	std::lock_guard< std::mutex > shard_lock( p -> shard_mtx );
-	struct DeviceKeep
-	{
-		int keep;
-		DeviceKeep() : keep( 0 ) { (void) hipGetDevice( &keep ); }
-		~DeviceKeep() { (void) hipSetDevice( keep ); }
-	} devkeep;
+	DeviceGuard devkeep;
 	std::vector< avirhip_plan* > pl( n_gpus );
 	std::vector< int > r0( n_gpus ), r1( n_gpus );
 	std::vector< char* > band( n_gpus );
@@ -2971,7 +3060,7 @@ try
 	}
 
 	return( exec_any( p, src_rows, src_mem, dst_band, dst_mem, row0, row1,
-		stream, false, first_row, n_rows ));
+		stream, first_row, n_rows ));
 }
 AVIRHIP_CATCH( avirhip_resize_window )
 
@@ -2987,7 +3076,17 @@ try
 	}
 
 	hipStream_t st = (hipStream_t) stream;
-	hipEvent_t e0, e1;
+	// (destroyed on every way out)
+	struct Events
+	{
+		hipEvent_t e0, e1;
+		~Events()
+		{
+			if( e0 != nullptr ) (void) hipEventDestroy( e0 );
+			if( e1 != nullptr ) (void) hipEventDestroy( e1 );
+		}
+	} ev = { nullptr, nullptr };
+	hipEvent_t& e0 = ev.e0, & e1 = ev.e1;
 	AVIRHIP_HIPCHECK( hipEventCreate( &e0 ));
 	AVIRHIP_HIPCHECK( hipEventCreate( &e1 ));
 	AVIRHIP_HIPCHECK( hipEventRecord( e0, st ));
@@ -3007,8 +3106,6 @@ try
 	AVIRHIP_HIPCHECK( hipEventSynchronize( e1 ));
 	float ms = 0.0f;
 	AVIRHIP_HIPCHECK( hipEventElapsedTime( &ms, e0, e1 ));
-	(void) hipEventDestroy( e0 );
-	(void) hipEventDestroy( e1 );
 	*avg_ms = (double) ms / iters;
 	return( AVIRHIP_OK );
 }
