@@ -417,28 +417,13 @@ __global__ void __launch_bounds__( 64 ) k_gh( const GHParams P )
 // host side
 // ---------------------------------------------------------------------
 
-// sacc.hip: the streaming-accumulation kernel of downsizing axes
-struct SAData;
-int sacc_prepare_axis( const GPAxisHost& H, std::vector< void* >& allocs,
-	SAData** out );
-void sacc_release_axis( SAData* D );
-int sacc_run_axis( const SAData* D, bool rows, const void* src, int src_type,
-	int src_ch, int live_ch, long s_lane, long s_step, float* dst, long d_lane,
-	long d_step, int lane_lo, int lane_hi, int out_lo, int out_hi,
-	hipStream_t st, const GPOut* out = nullptr, bool finite = false,
-	bool ladder = false, bool must_two = false,
-	unsigned int* flag_set = nullptr, const unsigned int* guard = nullptr );
-bool sacc_has_two( const SAData* D );
-bool sacc_is_zs( const SAData* D );
-double sacc_k( const SAData* D );
-
 // Whether a pass takes the accumulation kernel where the axis has one. Axes
 // that downsize by 1 < k < 2 (13 .. 25 taps over the zero-stuffed view) have had
 // one since round 4; measured against the gather kernels on one box
 // (3840x2160 sources): RGB uint8 k = 1.5 0.109 vs 0.151 ms, k = 1.92 0.099 vs
 // 0.141; float RGBA on the EXACT kernels k = 1.5 0.118 vs 0.122, k = 1.75 0.109
 // vs 0.113, k = 1.92 0.111 vs 0.116 -- `always`: integer and float RGBA
-// sources. Float pixels of 1-3 channels run optimistically (gpass_run: two
+// sources. Float pixels of 1-3 channels run optimistically (gpass_route: two
 // more launches) and take it from k = 1.7 on (RGBA, optimistic: k = 1.5 0.139
 // vs 0.126, k = 1.75 0.113 vs 0.115, k = 1.92 0.111 vs 0.118).
 // Round 6: FLOAT RGBA sources on 1 < k < 2 axes go back to the gather kernels
@@ -452,7 +437,7 @@ double sacc_k( const SAData* D );
 // branch-free accumulation kernels, which read them raw (RGB uint8 k = 1.5:
 // 0.104 vs 0.133). AVIRHIP_SA_ZS_FRGBA=1: the round-5 routing (A/B).
 static bool sa_wanted( const SAData* sa, const bool always,
-	const bool frgba = false )
+	const bool frgba )
 {
 	static const double kmin = ( getenv( "AVIRHIP_SA_ZS_KMIN" ) != nullptr ?
 		atof( getenv( "AVIRHIP_SA_ZS_KMIN" )) : 1.7 ); // (tuning aid)
@@ -497,6 +482,20 @@ static int next_pow2( int v )
 	int p = 2;
 	while( p < v ) p <<= 1;
 	return( p );
+}
+
+// Whether the gather kernels can run an axis of a call, from the plan's data
+// alone. Horizontal: the strips exist; a raw source is read in at most four
+// pieces a row, by the AVIR variants only. Vertical: the rings fit; an output
+// stage handles whole pixels, whose rings are twice as long.
+static bool h_gather_takes( const GPData* D, const bool has_raw )
+{
+	return( D -> h_geom && ( !has_raw || ( D -> h_nseg <= 4 && !D -> h.a.lanc )));
+}
+
+static bool v_gather_takes( const GPData* D, const bool has_out )
+{
+	return( D -> v_geom && ( !has_out || gv_whole_px_fits( D -> v_rs, D -> v_rc )));
 }
 
 // Recognises PRE / POST / NONE in a lowered AVIR axis.
@@ -1199,11 +1198,11 @@ static void launch_gh( const GHParams& P, int src_kind, int items, size_t lds,
 	}
 }
 
-static int run_h( const GPData* D, const float* src, long src_ss, int src_w,
-	float* dst, long dst_ss, int dst_row0, int dst_w, int row_lo, int row_hi,
-	hipStream_t st, const void* raw = nullptr, int raw_type = 0,
-	int raw_ch = 0, long raw_stride = 0, const GPLOut* lout = nullptr )
+// One horizontal gather pass (k_gh, k_gh2). 1: the pass cannot read `G.raw`.
+static int run_h( const GPData* D, const GPPass& G, hipStream_t st )
 {
+	const ImageRef* const raw = G.raw;
+	const int row_lo = G.row_lo, row_hi = G.row_hi;
 	GHParams P;
 	memset( &P.lout, 0, sizeof( P.lout ));
 	P.dbg = 0;
@@ -1212,29 +1211,36 @@ static int run_h( const GPData* D, const float* src, long src_ss, int src_w,
 		atoi( getenv( "AVIRHIP_GP_DBG" )) : 0 );
 #endif
 
-	if( lout != nullptr )
+	if( G.lout != nullptr )
 	{
-		P.lout = *lout;
+		P.lout = *G.lout;
 	}
 
-	P.raw = raw; P.raw_ss = raw_stride; P.raw_ch = raw_ch;
-	const int src_kind = ( raw == nullptr ? 0 : ( raw_type == AVIRHIP_U8 ? 1 :
-		( raw_type == AVIRHIP_U16 ? 2 : 3 )));
+	P.raw = nullptr; P.raw_ss = 0; P.raw_ch = 0; P.raw_elems = 0;
+	int src_kind = 0;
 
-	if( raw != nullptr && ( D -> h_nseg > 4 || D -> h.a.lanc ))
-	{
-		return( 1 );
-	}
-
-	P.raw_elems = (long) ( row_hi - 1 ) * raw_stride + (long) src_w * raw_ch;
-
-	if( raw != nullptr && P.raw_elems < 4 )
+	if( !h_gather_takes( D, raw != nullptr ))
 	{
 		return( 1 );
 	}
 
-	P.src = src; P.src_ss = src_ss; P.src_w = src_w;
-	P.dst = dst; P.dst_ss = dst_ss; P.dst_row0 = dst_row0; P.dst_w = dst_w;
+	if( raw != nullptr )
+	{
+		P.raw = raw -> ptr; P.raw_ss = raw -> stride; P.raw_ch = raw -> ch;
+		src_kind = ( raw -> type == AVIRHIP_U8 ? 1 :
+			( raw -> type == AVIRHIP_U16 ? 2 : 3 ));
+		P.raw_elems = (long) ( row_hi - 1 ) * raw -> stride +
+			(long) G.src_w * raw -> ch;
+
+		if( P.raw_elems < 4 )
+		{
+			return( 1 );
+		}
+	}
+
+	P.src = G.src; P.src_ss = G.src_ss; P.src_w = G.src_w;
+	P.dst = G.dst; P.dst_ss = G.dst_ss; P.dst_row0 = G.dst_row0;
+	P.dst_w = G.dst_w;
 	P.ax = D -> h.a;
 	P.row_lo = row_lo; P.row_hi = row_hi;
 
@@ -1252,7 +1258,7 @@ static int run_h( const GPData* D, const float* src, long src_ss, int src_w,
 	const int gh2_min_nt = ( getenv( "AVIRHIP_GH2_MIN_NT" ) != nullptr ?
 		atoi( getenv( "AVIRHIP_GH2_MIN_NT" )) : 22 );
 
-	if( D -> h2_ow != 0 && raw == nullptr && lout == nullptr &&
+	if( D -> h2_ow != 0 && raw == nullptr && G.lout == nullptr &&
 		P.ax.nt >= gh2_min_nt && getenv( "AVIRHIP_NO_GH2" ) == nullptr )
 	{
 		P.nstrips = D -> h2_nstrips; P.ow = D -> h2_ow;
@@ -1361,43 +1367,19 @@ static void v_source_rows( const GPData* D, int row0, int row1, int& a, int& b )
 	b = std::max( 0, std::min( b, A.in_len - 1 ));
 }
 
-// Runs both passes for output rows [row0, row1) of a float RGBA plan. Returns
-// 1 when the call cannot take this path (alignment), so that the caller falls
-// back.
-// LANCIR (an inner plan): whether its vertical pass -- the first one -- can
-// read the owner's integer / narrower image itself (whole-pixel lanes).
-// Whether the vertical pass of a LANCIR plan reads the owner's image as it is
-// (`raw`: element type, channels, elements per row): its rows travel as bytes
-// by LDS-DMA, so the base and the row pitch have to be dword-aligned, the image
-// under 2 GiB, and the tap count one of the register-window variants of k_gv
-// (the LDS-window form keeps a ring of float pixels).
+// LANCIR (an inner plan): whether its vertical pass -- the first one -- reads
+// the owner's integer / narrower image as it is (whole-pixel lanes of the
+// register-window variants of k_gv: gpass_v_raw_ok).
 bool gpass_lancir_takes_raw( const avirhip_plan* p, const ImageRef& img )
 {
-	const void* const raw = img.ptr;
-	const int type = img.type;
-	const int ch = img.ch;
-	const long stride = img.stride;
 	const GPData* D = (const GPData*) p -> gpass;
 	const int lpath = ( p -> path != 0 ? p -> path : p -> auto_path );
-	const long esz = ( type == AVIRHIP_U8 ? 1 : ( type == AVIRHIP_U16 ? 2 : 4 ));
 	static const bool off = ( getenv( "AVIRHIP_GV_RAWDMA" ) != nullptr &&
 		atoi( getenv( "AVIRHIP_GV_RAWDMA" )) == 0 ); // (A/B: the pack pass instead)
 
-	if( D == nullptr || off )
-	{
-		return( false );
-	}
-
-	const int nt = D -> v.a.nt;
-
-	return( p -> is_lancir && lpath == 5 && D -> v_geom &&
-		D -> h_geom && p -> src_w > 48 &&
-		( D -> v_rs + D -> v_rc ) * 1024 + GV_QB + 6 * 1024 <= 64 * 1024 &&
-		nt >= 6 && nt <= 24 && ( nt & 1 ) == 0 &&
-		( (uintptr_t) raw & 3 ) == 0 && (( stride * esz ) & 3 ) == 0 &&
-		// (the DMA's num_records is this rounded up to a dword, in an int)
-		( (long) ( p -> src_h - 1 ) * stride + (long) p -> src_w * ch ) * esz <=
-		0x7ffffffcL );
+	return( D != nullptr && !off && p -> is_lancir && lpath == 5 &&
+		D -> v_geom && D -> h_geom && p -> src_w > 48 &&
+		gpass_v_raw_ok( D -> v.a, D -> v_rs, D -> v_rc, img, p -> src_w ));
 }
 
 // Whether the first pass reads the caller's image as it is (integer types,
@@ -1411,7 +1393,7 @@ bool gpass_takes_raw( const avirhip_plan* p )
 	return( D != nullptr && !p -> is_lancir &&
 		( sa_wanted( D -> sa_h, int_src || ( p -> in_type == AVIRHIP_F32 &&
 		p -> io_ch == 4 ), p -> in_type == AVIRHIP_F32 && p -> io_ch == 4 ) ||
-		( D -> h_geom && D -> h_nseg <= 4 )));
+		h_gather_takes( D, true )));
 }
 
 // the owner's output stage (LancirOut) as the kernels' store parameters
@@ -1426,6 +1408,451 @@ static GPLOut gp_make_lout( const avirhip_plan* p, const LancirOut& o )
 	return( L );
 }
 
+// ---- the route of one call (gpass_route): decided once, as data,
+// before anything is launched or allocated (the first row that holds)
+//
+//   outcome        plan     condition                                       launches
+//   refuse         LANCIR   an axis without its gather geometry             --
+//   need dst       LANCIR   no result buffer and no owner's output stage    --
+//   lanc fused     LANCIR   k_lf's strips exist, the fusion pays (lf_pays),   k_lf
+//                           k_lf reads `raw` if there is one, not UPG_TWO_PASS
+//   lanc two-pass  LANCIR   otherwise (a refused `raw`: AVIRHIP_NEED_SRC)     k_gv, k_gh
+//   avir fused     AVIR     12-tap upsizing on both axes from float RGBA,   k_gf
+//                           7 Mpixels of output or UPG_FUSED, not UPG_TWO_PASS
+//   refuse         AVIR     an axis on the gather kernels (sa_wanted says     --
+//                           no) without their geometry; a raw source into
+//                           k_gh strips of more than 4 pieces; an output
+//                           stage on k_gv rings too long for whole-pixel lanes
+//   optimistic     AVIR     a float source that is not float RGBA (or       k_sacc2v x2,
+//                           SACC_OPTIMISTIC), both axes on the branch-free   k_sacc x2
+//                           accumulation kernels, no SACC_LADDER
+//   avir two-pass  AVIR     otherwise: per axis the accumulation kernels    k_sacc* or k_gh /
+//                           (exact; integer sources: finite, or ladder)     k_gh2, k_sacc* or
+//                           or the gather kernels                           k_gv
+//
+// An accumulation pass that refuses a call's pointers (sacc_run_axis: 1) falls
+// back to the gather kernels of its axis, an optimistic run to the two-pass one.
+enum GPOutcome { GPR_REFUSE, GPR_NEED_DST, GPR_LANC_FUSED, GPR_LANC_TWO_PASS,
+	GPR_AVIR_FUSED, GPR_AVIR_OPTIMISTIC, GPR_AVIR_TWO_PASS };
+enum GPFamily { GPF_GATHER, GPF_ACC };
+enum GPAccForm { GPA_EXACT, GPA_FINITE, GPA_LADDER };
+
+struct GPRoute
+{
+	GPOutcome outcome;
+	GPFamily h, v;   // AVIR two-pass, optimistic: the kernels of each axis ...
+	GPAccForm form;  // ... and the form the two-pass accumulation kernels run in
+	bool need_mid;   // the intermediate image between two passes
+	bool need_alarm; // the plan's alarm word
+};
+
+// `raw`, `lout`: gpass_run's; `has_out`: its `iout != nullptr`. No HIP call,
+// no allocation.
+static const GPRoute gp_refuse = { GPR_REFUSE, GPF_GATHER, GPF_GATHER,
+	GPA_EXACT, false, false };
+
+static GPRoute route_lancir( const avirhip_plan* p, const GPData* D,
+	const float* dst, const ImageRef* raw, const LancirOut* lout,
+	const double lf_ratio )
+{
+	GPRoute R = gp_refuse;
+	const bool two_pass = (( p -> variant & AVIRHIP_VARIANT_UPG_TWO_PASS ) != 0 );
+	const bool fused = (( p -> variant & AVIRHIP_VARIANT_UPG_FUSED ) != 0 );
+
+	// Upsizing from float RGBA pixels: both passes in ONE launch (lfuse.hip)
+	// -- LANCIR's vertical-first order makes the fusion free of recomputation
+	// (with the owner's image as the source where its rows can travel as
+	// bytes). With an INTEGER result the fusion pays up to about 2.7x
+	// horizontally (RGBA: 3.2x): the vertical
+	// stage works on the 64 / ratio + 6 source columns of a strip's 64 lanes,
+	// and the two pass kernels' intermediate image is no longer small against a
+	// uint8 result (1920x1080 RGB uint8, same box, fused / two passes: x1.5
+	// 0.028 / 0.034 ms, x2.1 0.047 / 0.051, x2.5 0.064 / 0.065, x3 0.092 /
+	// 0.086, x4 0.166 / 0.136; RGBA uint8 x3 0.086 / 0.088, x4 0.152 / 0.140;
+	// float results: fused wins at every ratio, x3 0.082 / 0.126;
+	// profiles/r05_lanc, tools/rounds/r05_lf2.sh; lf_ratio >= 0 replaces both)
+	const bool lf_pays = ( lout == nullptr || lout -> type == AVIRHIP_F32 ||
+		(double) p -> new_w <= (double) p -> src_w * ( lf_ratio >= 0.0 ?
+		lf_ratio : ( lout -> ch == 4 ? 3.2 : 2.7 )) || fused );
+	const bool use_lf = ( D -> lf_ow != 0 && lf_pays && ( raw == nullptr ||
+		lfuse_takes_raw( *raw, p -> src_h, p -> src_w )) && !two_pass );
+
+	if( !D -> h_geom || !D -> v_geom )
+	{
+		return( R );
+	}
+
+	R.outcome = ( dst == nullptr && lout == nullptr ? GPR_NEED_DST :
+		use_lf ? GPR_LANC_FUSED : GPR_LANC_TWO_PASS );
+	R.need_mid = ( R.outcome == GPR_LANC_TWO_PASS );
+	return( R );
+}
+
+static GPRoute route_avir( const avirhip_plan* p, const GPData* D,
+	const ImageRef* raw, const bool has_out, const long gf_minpix )
+{
+	GPRoute R = gp_refuse;
+	const bool two_pass = (( p -> variant & AVIRHIP_VARIANT_UPG_TWO_PASS ) != 0 );
+	// (a forced variant bit 4 = "fused whatever the size": tests)
+	const bool fused = (( p -> variant & AVIRHIP_VARIANT_UPG_FUSED ) != 0 );
+
+	// Large upsizing plans of float RGBA sources run both passes in one launch
+	// (gfuse.hip): no intermediate image. "Large": a fused chunk repeats the
+	// horizontal arithmetic of its 18-row vertical run-in, which the saved
+	// FltBuf round trip only pays for once the frame is memory-heavy -- measured
+	// (tools/gf_sweep.py, fused / two-pass, profiles/r04_upg/gf_sweep.txt):
+	// 1920x1080 x1.3 1.06, x1.6 0.99, x1.9 0.94, x2.3 0.90, x3.0 0.78;
+	// 3840x2160 x1.15 0.92, x1.6 0.71; 1280x720 x2.3 1.01, x3.0 0.97 -- the
+	// crossing is at about 7 Mpixels of output.
+	// AVIRHIP_GF_MINPIX moves it (0: always), AVIRHIP_VARIANT_UPG_TWO_PASS
+	// keeps the two pass kernels (tests, A/B timing).
+	const bool use_gf = ( D -> h.a.mode == GP_PRE &&
+		D -> v.a.mode == GP_PRE && D -> h.a.nt == 12 && D -> v.a.nt == 12 &&
+		D -> h_geom && raw == nullptr && !two_pass &&
+		((long) p -> new_w * p -> new_h >= gf_minpix || fused ) &&
+		getenv( "AVIRHIP_NO_GFUSE" ) == nullptr );
+
+	if( use_gf )
+	{
+		R.outcome = GPR_AVIR_FUSED;
+		return( R );
+	}
+
+	// an integer image is finite, and so is the FltBuf made from it: both
+	// passes may take the branch-free form of the accumulation kernel
+	const bool int_src = ( raw != nullptr && ( raw -> type == AVIRHIP_U8 ||
+		raw -> type == AVIRHIP_U16 ));
+	const bool ladder = (( p -> variant & AVIRHIP_VARIANT_SACC_LADDER ) != 0 );
+
+	// Float sources, both axes streaming: OPTIMISTIC execution. The branch-free
+	// kernels are exact for finite samples only; they run first, the last pass
+	// raises the plan's alarm word when it emits a NaN or Inf (any non-finite
+	// sample inside the call's windows ends up in one: c * Inf and 0 * Inf are
+	// never finite; so does an overflow), and the exact kernels follow in the
+	// stream behind the alarm -- empty launches for finite images, a complete
+	// recomputation of both passes otherwise. (5184x3456 -> 1920x1280 float RGBA:
+	// 0.265 ms on the tiles, 0.15 ms this way.)
+	// Float RGBA sources (raw == nullptr: they travel by LDS-DMA) do NOT run
+	// optimistically unless asked to (AVIRHIP_VARIANT_SACC_OPTIMISTIC): their
+	// exact kernels are as fast as the branch-free ones (5184x3456 -> 1920x1280:
+	// 127 + 59 us against 131 + 59, profiles/r04_sacc/exact_vs_optimistic.txt)
+	// and the two launches behind the alarm cost 9 us a frame. Float pixels of
+	// 1-3 channels gain: 0.273 -> 0.198 ms for the same frame as float RGB.
+	static const bool no_opt = ( getenv( "AVIRHIP_NO_SACC_OPT" ) != nullptr );
+	const bool fsrc = ( raw != nullptr ? raw -> type == AVIRHIP_F32 : true );
+	static const bool opt_rgba = ( getenv( "AVIRHIP_SACC_OPT_RGBA" ) != nullptr &&
+		atoi( getenv( "AVIRHIP_SACC_OPT_RGBA" )) != 0 ); // (tuning aid)
+	const bool opt_wanted = ( raw != nullptr || opt_rgba ||
+		( p -> variant & AVIRHIP_VARIANT_SACC_OPTIMISTIC ) != 0 );
+
+	// (raw == nullptr: float RGBA -- the exact kernels unless the variant asks)
+	const bool sa_always = ( int_src || ( raw == nullptr && !opt_wanted ));
+	// (raw == nullptr: a float RGBA source)
+	const bool use_sa_h = sa_wanted( D -> sa_h, sa_always, raw == nullptr );
+	const bool use_sa_v = sa_wanted( D -> sa_v, sa_always, raw == nullptr );
+
+	R.h = ( use_sa_h ? GPF_ACC : GPF_GATHER );
+	R.v = ( use_sa_v ? GPF_ACC : GPF_GATHER );
+	R.form = ( !int_src ? GPA_EXACT : ladder ? GPA_LADDER : GPA_FINITE );
+
+	// what the plan's data alone refuse, before the first launch
+	if(( !use_sa_h && !h_gather_takes( D, raw != nullptr )) ||
+		( !use_sa_v && !v_gather_takes( D, has_out )))
+	{
+		return( R );
+	}
+
+	const bool optimistic = ( !int_src && fsrc && !ladder && !no_opt &&
+		opt_wanted && use_sa_h && use_sa_v && sacc_has_two( D -> sa_h ) &&
+		sacc_has_two( D -> sa_v ));
+
+	R.outcome = ( optimistic ? GPR_AVIR_OPTIMISTIC : GPR_AVIR_TWO_PASS );
+	R.need_mid = true;
+	R.need_alarm = optimistic;
+	return( R );
+}
+
+// (both tuning aids are read by the first call of any plan)
+static GPRoute gpass_route( const avirhip_plan* p, const GPData* D,
+	const float* dst, const ImageRef* raw, const bool has_out,
+	const LancirOut* lout )
+{
+	static const long gf_minpix = ( getenv( "AVIRHIP_GF_MINPIX" ) != nullptr ?
+		atol( getenv( "AVIRHIP_GF_MINPIX" )) : 7000000L );
+	static const double lf_ratio = ( getenv( "AVIRHIP_LF_INT_RATIO" ) != nullptr ?
+		atof( getenv( "AVIRHIP_LF_INT_RATIO" )) : -1.0 );
+
+	return( p -> is_lancir ? route_lancir( p, D, dst, raw, lout, lf_ratio ) :
+		route_avir( p, D, raw, has_out, gf_minpix ));
+}
+
+// ---- one function per outcome. What belongs to the call:
+struct GPCall
+{
+	const float* src; long src_stride; // float RGBA rows, unless `raw`
+	float* dst;                        // the float result's first band row
+	long dst_ss;
+	int row0, row1;
+	const ImageRef* raw;    // the image the first pass reads instead of `src`
+	const GPOut* out;       // AVIR: the last pass stores the caller's pixels
+	const LancirOut* lout;  // LANCIR: the last pass runs the owner's output stage
+	hipStream_t st;
+};
+
+// LANCIR, both passes in one launch (k_lf)
+static int run_lanc_fused( const avirhip_plan* p, const GPData* D,
+	const GPCall& C )
+{
+	LFParams G;
+	memset( &G, 0, sizeof( G ));
+	G.src = C.src; G.src_ss = C.src_stride;
+	G.dst = C.dst; G.dst_ss = C.dst_ss; G.dst_row0 = C.row0;
+	G.hx = D -> h.a; G.vx = D -> v.a;
+	G.row_lo = C.row0; G.row_hi = C.row1;
+	G.nstrips = D -> lf_nstrips; G.ow = D -> lf_ow;
+	G.seg = D -> d_lfseg; G.vtab = D -> d_lfvtab;
+
+	if( C.raw != nullptr )
+	{
+		// (an inner plan: the owner's image, read as it is)
+		const int esz = (int) dtype_size( C.raw -> type );
+
+		G.raw = C.raw -> ptr; G.raw_ss = C.raw -> stride;
+		G.raw_kind = ( esz == 1 ? 1 : ( esz == 2 ? 2 : 3 ));
+		G.raw_ch = C.raw -> ch; G.raw_bpp = esz * C.raw -> ch;
+		G.raw_bytes = image_dma_bytes( *C.raw, p -> src_h, p -> src_w );
+		G.raw_tdn = ( 64 * G.raw_bpp + ( G.raw_bpp & 3 ? 3 : 0 ) + 255 ) >> 8;
+	}
+
+	if( C.lout != nullptr )
+	{
+		G.lout = gp_make_lout( p, *C.lout );
+	}
+
+	return( lfuse_launch( G, C.st ));
+}
+
+// LANCIR, vertical first (lancir.h:601-646): mid = [new_h][src_w], only the
+// rows of the band
+static int run_lanc_two_pass( const avirhip_plan* p, const GPData* D,
+	const GPCall& C )
+{
+	GPPass V;
+	memset( &V, 0, sizeof( V ));
+	V.src = C.src; V.src_ss = C.src_stride; V.src_w = p -> src_w;
+	V.dst = D -> mid; V.dst_ss = (long) p -> src_w * 4; V.dst_row0 = 0;
+	V.dst_w = p -> src_w;
+	V.row_lo = C.row0; V.row_hi = C.row1;
+	V.raw = C.raw; // (an inner plan: the owner's image, read as it is)
+
+	const int rc = gpass_run_v( D -> v.a, D -> v_blk, D -> v_rs, D -> v_rc, V,
+		C.st );
+
+	if( rc != 0 )
+	{
+		// (the kernel refuses the image after all: the owner makes the float
+		// copy and calls again)
+		return( rc == 1 && C.raw != nullptr ? AVIRHIP_NEED_SRC : rc );
+	}
+
+	GPPass H;
+	memset( &H, 0, sizeof( H ));
+	H.src = D -> mid; H.src_ss = V.dst_ss; H.src_w = p -> src_w;
+	H.dst = C.dst; H.dst_ss = C.dst_ss; H.dst_row0 = C.row0;
+	H.dst_w = p -> new_w;
+	H.row_lo = C.row0; H.row_hi = C.row1;
+	// (an inner plan: the outer plan's output stage goes into the store of
+	// this pass, its result rows are never written)
+	GPLOut L;
+
+	if( C.lout != nullptr )
+	{
+		L = gp_make_lout( p, *C.lout );
+		H.lout = &L;
+	}
+
+	return( run_h( D, H, C.st ));
+}
+
+// AVIR, upsizing on both axes from a float RGBA source: ONE launch runs both
+// passes (k_gf), FltBuf never exists
+static int run_avir_fused( const avirhip_plan* p, const GPData* D,
+	const GPCall& C )
+{
+	GFParams G;
+	memset( &G, 0, sizeof( G ));
+	G.src = C.src; G.src_ss = C.src_stride;
+	G.dst = C.dst; G.dst_ss = C.dst_ss; G.dst_row0 = C.row0;
+	G.hx = D -> h.a; G.vx = D -> v.a;
+	G.row_lo = C.row0; G.row_hi = C.row1;
+	G.nstrips = D -> h_nstrips; G.ow = D -> h_ow;
+	G.seg = D -> d_hseg; G.nseg = D -> h_nseg;
+	G.sbuf = D -> h_sbuf; G.mbuf = D -> h_mbuf;
+
+	if( C.out != nullptr )
+	{
+		G.out = *C.out;
+	}
+
+	return( gfuse_launch( G, (double) p -> src_h / p -> new_h, C.st ));
+}
+
+// AVIR's passes: horizontal first into mid = FltBuf [src_h][new_w], only the
+// source rows [a, b] the band's vertical windows read (v_source_rows).
+
+static int avir_h_acc( const avirhip_plan* p, const GPData* D, const GPCall& C,
+	const int a, const int b, const SAForm& F )
+{
+	SAPass G;
+	G.rows = true;
+	G.dst = D -> mid; G.d_lane = (long) p -> new_w * 4; G.d_step = 4;
+	G.lane_lo = a; G.lane_hi = b + 1; G.out_lo = 0; G.out_hi = p -> new_w;
+	G.out = nullptr;
+
+	if( C.raw != nullptr )
+	{
+		const long es = (long) dtype_size( C.raw -> type );
+
+		G.src = C.raw -> ptr; G.src_type = C.raw -> type;
+		G.src_ch = C.raw -> ch; G.live_ch = C.raw -> ch;
+		G.s_lane = C.raw -> stride * es; G.s_step = C.raw -> ch * es;
+	}
+	else
+	{
+		G.src = C.src; G.src_type = AVIRHIP_F32; G.src_ch = 4;
+		G.live_ch = p -> io_ch;
+		G.s_lane = C.src_stride * 4; G.s_step = 16;
+	}
+
+	return( sacc_run_axis( D -> sa_h, G, F, C.st ));
+}
+
+static int avir_v_acc( const avirhip_plan* p, const GPData* D, const GPCall& C,
+	const SAForm& F )
+{
+	SAPass G;
+	G.rows = false;
+	G.src = D -> mid; G.src_type = AVIRHIP_F32; G.src_ch = 4;
+	G.live_ch = p -> io_ch;
+	G.s_lane = 16; G.s_step = (long) p -> new_w * 16;
+	G.dst = C.dst - (long) C.row0 * C.dst_ss; G.d_lane = 4; G.d_step = C.dst_ss;
+	G.lane_lo = 0; G.lane_hi = p -> new_w; G.out_lo = C.row0; G.out_hi = C.row1;
+	G.out = C.out;
+	return( sacc_run_axis( D -> sa_v, G, F, C.st ));
+}
+
+// k_sacc alone, no alarm
+static SAForm sa_exact()
+{
+	SAForm F;
+	F.finite = false; F.ladder = false; F.must_two = false;
+	F.alarm_set = nullptr; F.alarm_guard = nullptr;
+	return( F );
+}
+
+static int avir_h( const avirhip_plan* p, const GPData* D, const GPCall& C,
+	const GPFamily fam, const int a, const int b, const SAForm& F )
+{
+	int rc = ( fam == GPF_ACC ? avir_h_acc( p, D, C, a, b, F ) : 1 );
+
+	if( rc == 1 )
+	{
+		GPPass H;
+		memset( &H, 0, sizeof( H ));
+		H.src = C.src; H.src_ss = C.src_stride; H.src_w = p -> src_w;
+		H.dst = D -> mid; H.dst_ss = (long) p -> new_w * 4; H.dst_row0 = 0;
+		H.dst_w = p -> new_w;
+		H.row_lo = a; H.row_hi = b + 1;
+		H.raw = C.raw;
+		rc = run_h( D, H, C.st );
+	}
+
+	return( rc );
+}
+
+static int avir_v( const avirhip_plan* p, const GPData* D, const GPCall& C,
+	const GPFamily fam, const SAForm& F )
+{
+	int rc = ( fam == GPF_ACC ? avir_v_acc( p, D, C, F ) : 1 );
+
+	if( rc == 1 )
+	{
+		// (the route has answered this for an axis on the gather kernels: here
+		// only behind an accumulation pass that refused the call's pointers)
+		if( !v_gather_takes( D, C.out != nullptr ))
+		{
+			return( 1 );
+		}
+
+		GPPass V;
+		memset( &V, 0, sizeof( V ));
+		V.src = D -> mid; V.src_ss = (long) p -> new_w * 4; V.src_w = p -> new_w;
+		V.dst = C.dst; V.dst_ss = C.dst_ss; V.dst_row0 = C.row0;
+		V.dst_w = p -> new_w;
+		V.row_lo = C.row0; V.row_hi = C.row1;
+		V.out = C.out;
+		rc = gpass_run_v( D -> v.a, D -> v_blk, D -> v_rs, D -> v_rc, V, C.st );
+	}
+
+	return( rc );
+}
+
+static int run_avir_two_pass( const avirhip_plan* p, const GPData* D,
+	const GPCall& C, const GPRoute& R )
+{
+	SAForm F = sa_exact();
+	F.finite = ( R.form != GPA_EXACT );
+	F.ladder = ( R.form == GPA_LADDER );
+	int a, b;
+	v_source_rows( D, C.row0, C.row1, a, b );
+
+	const int rc = avir_h( p, D, C, R.h, a, b, F );
+	return( rc != 0 ? rc : avir_v( p, D, C, R.v, F ));
+}
+
+// AVIR, four launches: the branch-free kernels (the first lowers the alarm, the
+// second may raise it), then the exact kernels behind the alarm
+static int run_avir_optimistic( const avirhip_plan* p, const GPData* D,
+	const GPCall& C, const GPRoute& R )
+{
+	SAForm fast = sa_exact(), exact = sa_exact();
+	fast.finite = true; fast.must_two = true; fast.alarm_set = D -> nf_flag;
+	exact.alarm_guard = D -> nf_flag;
+	int a, b;
+	v_source_rows( D, C.row0, C.row1, a, b );
+
+	int rc = avir_h_acc( p, D, C, a, b, fast );
+	if( rc == 0 ) rc = avir_v_acc( p, D, C, fast );
+
+	if( rc == 0 )
+	{
+		rc = avir_h_acc( p, D, C, a, b, exact );
+		return( rc != 0 ? rc : avir_v_acc( p, D, C, exact ));
+	}
+
+	// (a pass cannot take the branch-free form: the exact kernels alone)
+	return( rc != 1 ? rc : run_avir_two_pass( p, D, C, R ));
+}
+
+template< class T >
+static int gp_lazy_alloc( avirhip_plan* p, GPData* D, T*& slot,
+	const size_t bytes, const bool counted )
+{
+	if( slot == nullptr )
+	{
+		void* q = nullptr;
+		AVIRHIP_HIPCHECK( hipMalloc( &q, bytes ));
+		D -> allocs.push_back( q );
+		if( counted ) p -> alloc_bytes += bytes;
+		slot = (T*) q;
+	}
+
+	return( AVIRHIP_OK );
+}
+
+// Runs output rows [row0, row1) of a float RGBA plan. Returns 1 when the call
+// cannot take this path (alignment, a pass this plan does not have), so that
+// the caller falls back.
 // `iout` != nullptr: the caller's integer image (the band's first row) -- the
 // last pass converts and stores there (no float result, no epilogue pass);
 // returns 1 if this plan's last pass cannot (the caller then runs unfused).
@@ -1454,13 +1881,11 @@ int gpass_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 		}
 
 		gp_make_out( p, iout, O );
-		dst = (float*) iout; // (alignment checks below: not written as floats)
 	}
-
-	const GPOut* const out = ( iout != nullptr ? &O : nullptr );
 
 	GPData* D = (GPData*) p -> gpass;
 
+	// (`dst` behind an output stage is never written: no alignment asked of it)
 	if( D == nullptr || ( iout == nullptr && ( (uintptr_t) dst & 15 )) ||
 		( p -> is_lancir && ( p -> new_stride & 3 )) ||
 		( raw == nullptr && (( (uintptr_t) src & 15 ) || ( src_stride & 3 ))) ||
@@ -1474,333 +1899,33 @@ int gpass_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 		return( AVIRHIP_OK );
 	}
 
-	// Large upsizing plans of float RGBA sources run both passes in one launch
-	// (gfuse.hip): no intermediate image. "Large": a fused chunk repeats the
-	// horizontal arithmetic of its 18-row vertical run-in, which the saved
-	// FltBuf round trip only pays for once the frame is memory-heavy -- measured
-	// (tools/gf_sweep.py, fused / two-pass, profiles/r04_upg/gf_sweep.txt):
-	// 1920x1080 x1.3 1.06, x1.6 0.99, x1.9 0.94, x2.3 0.90, x3.0 0.78;
-	// 3840x2160 x1.15 0.92, x1.6 0.71; 1280x720 x2.3 1.01, x3.0 0.97 -- the
-	// crossing is at about 7 Mpixels of output.
-	// AVIRHIP_GF_MINPIX moves it (0: always), AVIRHIP_VARIANT_UPG_TWO_PASS
-	// keeps the two pass kernels.
-	static const long gf_minpix = ( getenv( "AVIRHIP_GF_MINPIX" ) != nullptr ?
-		atol( getenv( "AVIRHIP_GF_MINPIX" )) : 7000000L );
-	// (a forced variant bit 4 = "fused whatever the size": tests)
-	const bool use_gf = ( !p -> is_lancir && D -> h.a.mode == GP_PRE &&
-		D -> v.a.mode == GP_PRE && D -> h.a.nt == 12 && D -> v.a.nt == 12 &&
-		D -> h_geom && raw == nullptr &&
-		( p -> variant & AVIRHIP_VARIANT_UPG_TWO_PASS ) == 0 &&
-		((long) p -> new_w * p -> new_h >= gf_minpix ||
-		( p -> variant & AVIRHIP_VARIANT_UPG_FUSED ) != 0 ) &&
-		getenv( "AVIRHIP_NO_GFUSE" ) == nullptr );
-
-	// ... and so do LANCIR's upsizing plans of float RGBA pixels (lfuse.hip)
-	// (with the owner's image as the source where its rows can travel as bytes
-	// -- what gpass_lancir_takes_raw promised covers it). With an INTEGER result
-	// the fusion pays up to about 2.7x horizontally (RGBA: 3.2x): the vertical
-	// stage works on the 64 / ratio + 6 source columns of a strip's 64 lanes,
-	// and the two pass kernels' intermediate image is no longer small against a
-	// uint8 result (1920x1080 RGB uint8, same box, fused / two passes: x1.5
-	// 0.028 / 0.034 ms, x2.1 0.047 / 0.051, x2.5 0.064 / 0.065, x3 0.092 /
-	// 0.086, x4 0.166 / 0.136; RGBA uint8 x3 0.086 / 0.088, x4 0.152 / 0.140;
-	// float results: fused wins at every ratio, x3 0.082 / 0.126;
-	// profiles/r05_lanc, tools/rounds/r05_lf2.sh)
-	static const double lf_ratio = ( getenv( "AVIRHIP_LF_INT_RATIO" ) != nullptr ?
-		atof( getenv( "AVIRHIP_LF_INT_RATIO" )) : -1.0 ); // (tuning aid)
-	const bool lf_pays = ( lout == nullptr || lout -> type == AVIRHIP_F32 ||
-		(double) p -> new_w <= (double) p -> src_w * ( lf_ratio >= 0.0 ?
-		lf_ratio : ( lout -> ch == 4 ? 3.2 : 2.7 )) ||
-		( p -> variant & AVIRHIP_VARIANT_UPG_FUSED ) != 0 );
-	const bool use_lf = ( p -> is_lancir && D -> lf_ow != 0 && lf_pays &&
-		( raw == nullptr || lfuse_takes_raw( raw -> ptr, raw -> type,
-		raw -> ch, raw -> stride, p -> src_h, p -> src_w )) &&
-		( p -> variant & AVIRHIP_VARIANT_UPG_TWO_PASS ) == 0 );
-
-	if( D -> mid == nullptr && !use_gf && !use_lf )
-	{
-		void* q = nullptr;
-		AVIRHIP_HIPCHECK( hipMalloc( &q, D -> mid_bytes ));
-		D -> allocs.push_back( q );
-		p -> alloc_bytes += D -> mid_bytes;
-		D -> mid = (float*) q;
-	}
-
-	const long dst_ss = ( p -> is_lancir ? p -> new_stride : (long) p -> new_w * 4 );
+	const GPRoute R = gpass_route( p, D, dst, raw, iout != nullptr, lout );
 	int rc;
 
-	if( p -> is_lancir )
+	if( R.need_mid && ( rc = gp_lazy_alloc( p, D, D -> mid, D -> mid_bytes,
+		true )) != 0 ) return( rc );
+
+	if( R.need_alarm && ( rc = gp_lazy_alloc( p, D, D -> nf_flag, 64,
+		false )) != 0 ) return( rc );
+
+	GPCall C;
+	C.src = src; C.src_stride = src_stride;
+	C.dst = dst;
+	C.dst_ss = ( p -> is_lancir ? p -> new_stride : (long) p -> new_w * 4 );
+	C.row0 = row0; C.row1 = row1;
+	C.raw = raw; C.out = ( iout != nullptr ? &O : nullptr ); C.lout = lout;
+	C.st = st;
+
+	switch( R.outcome )
 	{
-		if( !D -> h_geom || !D -> v_geom )
-		{
-			return( 1 );
-		}
-
-		if( dst == nullptr && lout == nullptr )
-		{
-			return( AVIRHIP_NEED_DST );
-		}
-
-		// Upsizing from float RGBA pixels: both passes in ONE launch
-		// (lfuse.hip) -- LANCIR's vertical-first order makes the fusion free of
-		// recomputation. AVIRHIP_VARIANT_UPG_TWO_PASS keeps the two kernels.
-		if( use_lf )
-		{
-			LFParams G;
-			memset( &G, 0, sizeof( G ));
-			G.src = src; G.src_ss = src_stride;
-			G.dst = dst; G.dst_ss = dst_ss; G.dst_row0 = row0;
-			G.hx = D -> h.a; G.vx = D -> v.a;
-			G.row_lo = row0; G.row_hi = row1;
-			G.nstrips = D -> lf_nstrips; G.ow = D -> lf_ow;
-			G.seg = D -> d_lfseg; G.vtab = D -> d_lfvtab;
-
-			if( raw != nullptr )
-			{
-				// (an inner plan: the owner's image, read as it is)
-				const int esz = ( raw -> type == AVIRHIP_U8 ? 1 :
-					( raw -> type == AVIRHIP_U16 ? 2 : 4 ));
-
-				G.raw = raw -> ptr; G.raw_ss = raw -> stride;
-				G.raw_kind = ( esz == 1 ? 1 : ( esz == 2 ? 2 : 3 ));
-				G.raw_ch = raw -> ch; G.raw_bpp = esz * raw -> ch;
-				// (rounded up to whole dwords, as in gpass_run_v)
-				G.raw_bytes = (int) (((( (long) ( p -> src_h - 1 ) * raw -> stride +
-					(long) p -> src_w * raw -> ch ) * esz ) + 3 ) & ~3L );
-				G.raw_tdn = ( 64 * G.raw_bpp + ( G.raw_bpp & 3 ? 3 : 0 ) + 255 ) >> 8;
-			}
-
-			if( lout != nullptr )
-			{
-				G.lout = gp_make_lout( p, *lout );
-			}
-
-			return( lfuse_launch( G, st ));
-		}
-
-		// vertical first (lancir.h:601-646): mid = [new_h][src_w], only the
-		// rows of the band
-		const long mid_ss = (long) p -> src_w * 4;
-
-		if( raw != nullptr )
-		{
-			// (an inner plan: the owner's image, read as it is)
-			rc = gpass_run_v( D -> v.a, D -> v_blk, D -> v_rs, D -> v_rc, src, src_stride, p -> src_w, D -> mid, mid_ss, 0,
-				row0, row1, st, nullptr, raw -> ptr, raw -> type,
-				raw -> ch, raw -> stride );
-
-			// (the kernel refused the image after all: the owner makes the
-			// float copy and calls again)
-			if( rc == 1 ) return( AVIRHIP_NEED_SRC );
-			if( rc != 0 ) return( rc );
-		}
-		else
-		if(( rc = gpass_run_v( D -> v.a, D -> v_blk, D -> v_rs, D -> v_rc, src, src_stride, p -> src_w, D -> mid, mid_ss, 0,
-			row0, row1, st )) != 0 ) return( rc );
-
-		if( lout != nullptr )
-		{
-			// (an inner plan: the outer plan's output stage goes into the
-			// store of this pass, its result rows are never written)
-			const GPLOut L = gp_make_lout( p, *lout );
-
-			return( run_h( D, D -> mid, mid_ss, p -> src_w, dst, dst_ss, row0,
-				p -> new_w, row0, row1, st, nullptr, 0, 0, 0, &L ));
-		}
-
-		if( dst == nullptr )
-		{
-			return( AVIRHIP_NEED_DST ); // (an inner plan run without a result buffer)
-		}
-
-		return( run_h( D, D -> mid, mid_ss, p -> src_w, dst, dst_ss, row0,
-			p -> new_w, row0, row1, st ));
+		case GPR_NEED_DST: return( AVIRHIP_NEED_DST );
+		case GPR_LANC_FUSED: return( run_lanc_fused( p, D, C ));
+		case GPR_LANC_TWO_PASS: return( run_lanc_two_pass( p, D, C ));
+		case GPR_AVIR_FUSED: return( run_avir_fused( p, D, C ));
+		case GPR_AVIR_OPTIMISTIC: return( run_avir_optimistic( p, D, C, R ));
+		case GPR_AVIR_TWO_PASS: return( run_avir_two_pass( p, D, C, R ));
+		default: return( 1 );
 	}
-
-	// Upsizing on both axes from a float RGBA source: ONE launch runs both
-	// passes (gfuse.hip), FltBuf never exists. AVIRHIP_VARIANT_UPG_TWO_PASS
-	// keeps the two pass kernels (tests, A/B timing).
-	if( use_gf )
-	{
-		GFParams G;
-		memset( &G, 0, sizeof( G ));
-		G.src = src; G.src_ss = src_stride;
-		G.dst = dst; G.dst_ss = dst_ss; G.dst_row0 = row0;
-		G.hx = D -> h.a; G.vx = D -> v.a;
-		G.row_lo = row0; G.row_hi = row1;
-		G.nstrips = D -> h_nstrips; G.ow = D -> h_ow;
-		G.seg = D -> d_hseg; G.nseg = D -> h_nseg;
-		G.sbuf = D -> h_sbuf; G.mbuf = D -> h_mbuf;
-
-		if( out != nullptr )
-		{
-			G.out = *out;
-		}
-
-		return( gfuse_launch( G, (double) p -> src_h / p -> new_h, st ));
-	}
-
-	// AVIR: horizontal first into mid = FltBuf [src_h][new_w], only the source
-	// rows the band's vertical windows read
-	const long mid_ss = (long) p -> new_w * 4;
-	int a, b;
-	v_source_rows( D, row0, row1, a, b );
-
-	rc = 1;
-	// an integer image is finite, and so is the FltBuf made from it: both
-	// passes may take the branch-free form of the accumulation kernel
-	// (the caller's image, for the kernels below)
-	const void* const rawp = ( raw != nullptr ? raw -> ptr : nullptr );
-	const int raw_type = ( raw != nullptr ? raw -> type : 0 );
-	const int raw_ch = ( raw != nullptr ? raw -> ch : 0 );
-	const long raw_stride = ( raw != nullptr ? raw -> stride : 0 );
-	const bool int_src = ( raw != nullptr && ( raw_type == AVIRHIP_U8 ||
-		raw_type == AVIRHIP_U16 ));
-	const bool ladder = (( p -> variant & AVIRHIP_VARIANT_SACC_LADDER ) != 0 );
-
-	// Float sources, both axes streaming: OPTIMISTIC execution. The branch-free
-	// kernels are exact for finite samples only; they run first, the last pass
-	// raises the plan's alarm word when it emits a NaN or Inf (any non-finite
-	// sample inside the call's windows ends up in one: c * Inf and 0 * Inf are
-	// never finite; so does an overflow), and the exact kernels follow in the
-	// stream behind the alarm -- empty launches for finite images, a complete
-	// recomputation of both passes otherwise. (5184x3456 -> 1920x1280 float RGBA:
-	// 0.265 ms on the tiles, 0.15 ms this way.)
-	// Float RGBA sources (raw == nullptr: they travel by LDS-DMA) do NOT run
-	// optimistically unless asked to (AVIRHIP_VARIANT_SACC_OPTIMISTIC): their
-	// exact kernels are as fast as the branch-free ones (5184x3456 -> 1920x1280:
-	// 127 + 59 us against 131 + 59, profiles/r04_sacc/exact_vs_optimistic.txt)
-	// and the two launches behind the alarm cost 9 us a frame. Float pixels of
-	// 1-3 channels gain: 0.273 -> 0.198 ms for the same frame as float RGB.
-	static const bool no_opt = ( getenv( "AVIRHIP_NO_SACC_OPT" ) != nullptr );
-	const bool fsrc = ( raw != nullptr ? raw_type == AVIRHIP_F32 : true );
-	static const bool opt_rgba = ( getenv( "AVIRHIP_SACC_OPT_RGBA" ) != nullptr &&
-		atoi( getenv( "AVIRHIP_SACC_OPT_RGBA" )) != 0 ); // (tuning aid)
-	const bool opt_wanted = ( raw != nullptr || opt_rgba ||
-		( p -> variant & AVIRHIP_VARIANT_SACC_OPTIMISTIC ) != 0 );
-
-	// (raw == nullptr: float RGBA -- the exact kernels unless the variant asks)
-	const bool sa_always = ( int_src || ( raw == nullptr && !opt_rgba &&
-		( p -> variant & AVIRHIP_VARIANT_SACC_OPTIMISTIC ) == 0 ));
-	// (raw == nullptr: a float RGBA source)
-	const bool use_sa_h = sa_wanted( D -> sa_h, sa_always, raw == nullptr );
-	const bool use_sa_v = sa_wanted( D -> sa_v, sa_always, raw == nullptr );
-
-	if( !int_src && fsrc && !ladder && !no_opt && opt_wanted && use_sa_h &&
-		use_sa_v &&
-		sacc_has_two( D -> sa_h ) && sacc_has_two( D -> sa_v ))
-	{
-		if( D -> nf_flag == nullptr )
-		{
-			void* q = nullptr;
-			AVIRHIP_HIPCHECK( hipMalloc( &q, 64 ));
-			D -> allocs.push_back( q );
-			D -> nf_flag = (unsigned int*) q;
-		}
-
-		// (the first optimistic pass lowers the alarm, the second may raise it)
-
-		auto h_pass = [&]( const bool fast ) -> int
-		{
-			if( raw != nullptr )
-			{
-				return( sacc_run_axis( D -> sa_h, true, rawp, raw_type, raw_ch,
-					raw_ch, raw_stride * 4, raw_ch * 4, D -> mid, mid_ss, 4, a,
-					b + 1, 0, p -> new_w, st, nullptr, fast, false, fast,
-					fast ? D -> nf_flag : nullptr, fast ? nullptr : D -> nf_flag ));
-			}
-
-			return( sacc_run_axis( D -> sa_h, true, src, AVIRHIP_F32, 4,
-				p -> io_ch, src_stride * 4, 16, D -> mid, mid_ss, 4, a, b + 1, 0,
-				p -> new_w, st, nullptr, fast, false, fast,
-				fast ? D -> nf_flag : nullptr, fast ? nullptr : D -> nf_flag ));
-		};
-
-		auto v_pass = [&]( const bool fast ) -> int
-		{
-			return( sacc_run_axis( D -> sa_v, false, D -> mid, AVIRHIP_F32, 4,
-				p -> io_ch, 16, mid_ss * 4, dst - (long) row0 * dst_ss, 4, dst_ss,
-				0, p -> new_w, row0, row1, st, out, fast, false, fast,
-				fast ? D -> nf_flag : nullptr, fast ? nullptr : D -> nf_flag ));
-		};
-
-		rc = h_pass( true );
-
-		if( rc == 0 )
-		{
-			rc = v_pass( true );
-
-			if( rc == 0 )
-			{
-				// (the exact kernels behind the alarm)
-				rc = h_pass( false );
-				if( rc == 0 ) rc = v_pass( false );
-				return( rc );
-			}
-		}
-
-		if( rc != 1 )
-		{
-			return( rc );
-		}
-		// (a pass cannot take the branch-free form: the exact kernels below)
-	}
-
-	rc = 1;
-
-	if( use_sa_h )
-	{
-		if( raw != nullptr )
-		{
-			const long es = ( raw_type == AVIRHIP_U8 ? 1 :
-				( raw_type == AVIRHIP_U16 ? 2 : 4 ));
-
-			rc = sacc_run_axis( D -> sa_h, true, rawp, raw_type, raw_ch, raw_ch,
-				raw_stride * es, raw_ch * es, D -> mid, mid_ss, 4, a, b + 1, 0,
-				p -> new_w, st, nullptr, int_src, ladder );
-		}
-		else
-		{
-			rc = sacc_run_axis( D -> sa_h, true, src, AVIRHIP_F32, 4, p -> io_ch,
-				src_stride * 4, 16, D -> mid, mid_ss, 4, a, b + 1, 0,
-				p -> new_w, st );
-		}
-	}
-
-	if( rc == 1 )
-	{
-		if( !D -> h_geom )
-		{
-			return( 1 );
-		}
-
-		rc = run_h( D, src, src_stride, p -> src_w, D -> mid, mid_ss, 0,
-			p -> new_w, a, b + 1, st, rawp, raw_type, raw_ch, raw_stride );
-	}
-
-	if( rc != 0 ) return( rc );
-
-	rc = 1;
-
-	if( use_sa_v )
-	{
-		rc = sacc_run_axis( D -> sa_v, false, D -> mid, AVIRHIP_F32, 4,
-			p -> io_ch, 16, mid_ss * 4, dst - (long) row0 * dst_ss, 4, dst_ss,
-			0, p -> new_w, row0, row1, st, out, int_src, ladder );
-	}
-
-	if( rc == 1 )
-	{
-		if( !D -> v_geom )
-		{
-			return( 1 );
-		}
-
-		rc = gpass_run_v( D -> v.a, D -> v_blk, D -> v_rs, D -> v_rc, D -> mid, mid_ss, p -> new_w, dst, dst_ss, row0, row0,
-			row1, st, out );
-	}
-
-	return( rc );
 }
 
 } // namespace avirhip

@@ -634,8 +634,8 @@ struct LFParams
 int lfuse_launch( LFParams& P, hipStream_t st );
 // gpass_h2.hip: k_gh2 (two gather outputs per lane); 1: no variant for the tap count
 int launch_gh2( const GHParams& P, int items, size_t lds, hipStream_t st );
-bool lfuse_takes_raw( const void* raw, int type, int ch, long stride,
-	int in_len_v, int width );
+// (`img`: rows of `width` pixels, `in_len_v` of them)
+bool lfuse_takes_raw( const ImageRef& img, int in_len_v, int width );
 
 // One gather output: tap t reads ld( t ); cf4( b ) returns the coefficients
 // of taps 4b .. 4b + 3 (rows are padded to a multiple of four; padded taps are
@@ -999,12 +999,72 @@ static inline int balanced_chunk( int rows, int nstrips, int min_chunk, int max_
 	return( best_chunk );
 }
 
+// One gather pass of one call (k_gh: run_h in gpass.hip; k_gv: gpass_run_v):
+// float RGBA rows in, float RGBA rows out. What a pass does not have stays
+// nullptr.
+struct GPPass
+{
+	const float* src; long src_ss; int src_w; // floats, pixels per row
+	float* dst; long dst_ss; int dst_row0, dst_w;
+	int row_lo, row_hi;   // rows to process (k_gh) / output rows (k_gv)
+	const ImageRef* raw;  // a first pass: the image it reads instead of `src`
+	const GPOut* out;     // k_gv as the last pass of an AVIR plan: its output stage
+	const GPLOut* lout;   // k_gh as the last pass of a LANCIR inner plan: its owner's
+};
+
 // gpassv.hip
+// whether whole-pixel lanes' rings of rs + rc rows fit a workgroup's LDS
+inline bool gv_whole_px_fits( const int rs, const int rc )
+{
+	return(( rs + rc ) * 1024 + GV_QB + 6 * 1024 <= 64 * 1024 );
+}
+// Whether k_gv reads `img` (rows of `width` pixels) as it lies: its rows travel
+// as bytes by LDS-DMA. The ONE test behind gpass_lancir_takes_raw's promise and
+// gpass_run_v's refusal.
+bool gpass_v_raw_ok( const GPAxis& A, int v_rs, int v_rc, const ImageRef& img,
+	int width );
+// (G.dst_w is not used: the pass keeps the width)
 int gpass_run_v( const GPAxis& A, int v_blk, int v_rs, int v_rc,
-	const float* src, long src_ss, int width, float* dst, long dst_ss,
-	int dst_row0, int row_lo, int row_hi, hipStream_t st,
-	const GPOut* out = nullptr, const void* raw = nullptr, int raw_type = 0,
-	int raw_ch = 0, long raw_stride = 0 );
+	const GPPass& G, hipStream_t st );
+
+// sacc.hip: the streaming-accumulation kernels of downsizing axes
+struct SAData;
+int sacc_prepare_axis( const GPAxisHost& H, std::vector< void* >& allocs,
+	SAData** out );
+void sacc_release_axis( SAData* D );
+bool sacc_has_two( const SAData* D );
+bool sacc_is_zs( const SAData* D );
+double sacc_k( const SAData* D );
+
+// One accumulation pass of one call: where its lanes and samples lie ...
+struct SAPass
+{
+	bool rows;            // the lanes are image rows (the horizontal pass)
+	const void* src;
+	int src_type, src_ch; // AVIRHIP_F32 with 4 channels travels by LDS-DMA
+	int live_ch;          // channels of a float RGBA source that carry data
+	long s_lane, s_step;  // bytes between lanes / samples
+	float* dst;
+	long d_lane, d_step;  // floats between lanes / outputs
+	int lane_lo, lane_hi, out_lo, out_hi;
+	const GPOut* out;     // nullptr: float RGBA results
+};
+
+// ... and the form it runs in. exact: k_sacc. finite: the source is known (an
+// integer image, the FltBuf made from one) or hoped (optimistic) to be finite
+// -- the branch-free kernels where the pass has them; with `ladder` k_sacc after
+// all (AVIRHIP_VARIANT_SACC_LADDER). must_two: refuse (1) rather than run k_sacc.
+// alarm_set: the optimistic passes lower (rows) and raise (columns) this word;
+// alarm_guard: k_sacc returns at once while it reads 0.
+struct SAForm
+{
+	bool finite, ladder, must_two;
+	unsigned int* alarm_set;
+	const unsigned int* alarm_guard;
+};
+
+int sacc_run_axis( const SAData* D, const SAPass& G, const SAForm& F,
+	hipStream_t st );
 
 } // namespace avirhip
 

@@ -38,46 +38,48 @@ static int launch_gv( const GVParams& P, int wp, int items, size_t lds,
 	return( 0 );
 }
 
-int gpass_run_v( const GPAxis& A_, int v_blk, int v_rs, int v_rc,
-	const float* src, long src_ss, int width, float* dst, long dst_ss,
-	int dst_row0, int row_lo, int row_hi, hipStream_t st, const GPOut* out,
-	const void* raw, int raw_type, int raw_ch, long raw_stride )
+bool gpass_v_raw_ok( const GPAxis& A, const int v_rs, const int v_rc,
+	const ImageRef& img, const int width )
 {
+	const long esz = (long) dtype_size( img.type );
+
+	// at least the four elements the loader's bound assumes; dword-aligned base
+	// and row pitch, under 2 GiB; a register-window variant of the LANCIR kernels
+	// (the LDS-window form keeps a ring of float pixels); whole-pixel lanes
+	return( (long) ( A.in_len - 1 ) * img.stride + (long) width * img.ch >= 4 &&
+		( (uintptr_t) img.ptr & 3 ) == 0 && (( img.stride * esz ) & 3 ) == 0 &&
+		image_dma_bytes( img, A.in_len, width ) != 0 &&
+		A.lanc && A.nt >= 6 && A.nt <= 24 && ( A.nt & 1 ) == 0 &&
+		gv_whole_px_fits( v_rs, v_rc ));
+}
+
+int gpass_run_v( const GPAxis& A_, int v_blk, int v_rs, int v_rc,
+	const GPPass& G, hipStream_t st )
+{
+	const ImageRef* const raw = G.raw;
+	const GPOut* const out = G.out;
+	const int width = G.src_w;
 	GVParams P;
 	memset( &P.out, 0, sizeof( P.out ));
-	P.raw = raw; P.raw_ss = raw_stride; P.raw_ch = raw_ch;
-	P.raw_kind = ( raw_type == AVIRHIP_U8 ? 1 : ( raw_type == AVIRHIP_U16 ? 2 : 3 ));
-	// (rows are raw_stride elements apart; the last one ends with its pixels)
-	P.raw_elems = (long) ( A_.in_len - 1 ) * raw_stride +
-		(long) width * raw_ch;
-
-	if( raw != nullptr && P.raw_elems < 4 )
-	{
-		return( 1 );
-	}
-
-	// raw rows travel as bytes by LDS-DMA (k_gv, LVAR bit 1): dword-aligned base
-	// and row pitch, under 2 GiB -- what gpass_lancir_takes_raw promised
-	P.raw_dma = 0; P.raw_bytes = 0;
+	P.raw = nullptr; P.raw_ss = 0; P.raw_ch = 0; P.raw_kind = 1;
+	P.raw_elems = 0; P.raw_dma = 0; P.raw_bytes = 0;
 
 	if( raw != nullptr )
 	{
-		const long esz = ( raw_type == AVIRHIP_U8 ? 1 :
-			( raw_type == AVIRHIP_U16 ? 2 : 4 ));
-		const long bytes = P.raw_elems * esz;
-		const int nt = A_.nt;
-
-		if(( (uintptr_t) raw & 3 ) != 0 || (( raw_stride * esz ) & 3 ) != 0 ||
-			bytes > 0x7ffffffcL || !A_.lanc || nt < 6 || nt > 24 || ( nt & 1 ))
+		// raw rows travel as bytes by LDS-DMA (k_gv, LVAR bit 1)
+		if( !gpass_v_raw_ok( A_, v_rs, v_rc, *raw, width ))
 		{
 			return( 1 );
 		}
 
-		P.raw_dma = (int) ( esz * raw_ch );
-		// (whole dwords: base and pitch are dword-aligned and device allocations
-		// dword-granular, so the row's last partial dword is fetched whichever
-		// way the range check treats a dword that straddles num_records)
-		P.raw_bytes = (int) (( bytes + 3 ) & ~3L );
+		P.raw = raw -> ptr; P.raw_ss = raw -> stride; P.raw_ch = raw -> ch;
+		P.raw_kind = ( raw -> type == AVIRHIP_U8 ? 1 :
+			( raw -> type == AVIRHIP_U16 ? 2 : 3 ));
+		// (rows are `stride` elements apart; the last one ends with its pixels)
+		P.raw_elems = (long) ( A_.in_len - 1 ) * raw -> stride +
+			(long) width * raw -> ch;
+		P.raw_dma = (int) dtype_size( raw -> type ) * raw -> ch;
+		P.raw_bytes = image_dma_bytes( *raw, A_.in_len, width );
 	}
 
 	if( out != nullptr )
@@ -85,29 +87,28 @@ int gpass_run_v( const GPAxis& A_, int v_blk, int v_rs, int v_rc,
 		P.out = *out;
 	}
 
-	P.src = src; P.src_ss = src_ss; P.width = width;
-	P.dst = dst; P.dst_ss = dst_ss; P.dst_row0 = dst_row0;
+	P.src = G.src; P.src_ss = G.src_ss; P.width = width;
+	P.dst = G.dst; P.dst_ss = G.dst_ss; P.dst_row0 = G.dst_row0;
 	P.ax = A_;
-	P.row_lo = row_lo; P.row_hi = row_hi;
+	P.row_lo = G.row_lo; P.row_hi = G.row_hi;
 	P.dbg = ( getenv( "AVIRHIP_GP_DBG" ) != nullptr ? atoi( getenv( "AVIRHIP_GP_DBG" )) : 0 );
 	P.blk = v_blk; P.rs = v_rs; P.rc = v_rc;
 
 	// whole-pixel lanes (64-pixel strips) wherever the image is wide enough
 	// to fill them and the rings stay within 64 KiB
-	int wp = ( width > 48 && ( P.rs + P.rc ) * 1024 + GV_QB + 6 * 1024 <= 64 * 1024 ?
-		2 : 1 );
+	int wp = ( width > 48 && gv_whole_px_fits( P.rs, P.rc ) ? 2 : 1 );
 
 	if( getenv( "AVIRHIP_GV_WP" ) != nullptr ) // tuning aid
 	{
 		wp = ( atoi( getenv( "AVIRHIP_GV_WP" )) == 2 &&
-			( P.rs + P.rc ) * 1024 + GV_QB + 6 * 1024 <= 64 * 1024 ? 2 : 1 );
+			gv_whole_px_fits( P.rs, P.rc ) ? 2 : 1 );
 	}
 
 	if( out != nullptr || raw != nullptr )
 	{
 		// the integer output stage and the raw-source loader handle whole
 		// pixels
-		if(( P.rs + P.rc ) * 1024 + GV_QB + 6 * 1024 > 64 * 1024 )
+		if( !gv_whole_px_fits( P.rs, P.rc ))
 		{
 			return( 1 );
 		}
@@ -147,7 +148,7 @@ int gpass_run_v( const GPAxis& A_, int v_blk, int v_rs, int v_rc,
 	// chunk height: a chunk's first window (NT rows, + 6 of FIR warm-up) is
 	// fed before its first output; its coefficient rows and positions live
 	// in LDS (<= 6 KiB)
-	const int rows = row_hi - row_lo;
+	const int rows = G.row_hi - G.row_lo;
 	const int ntp = ( P.ax.nt + 3 ) & ~3;
 	const int gextra = ( P.ax.mode == GP_POST ? 7 : 0 );
 	const int maxg = std::max( gextra + 1, 6144 / ( ntp * 4 + 4 ));

@@ -454,15 +454,14 @@ int lfuse_launch( LFParams& P, hipStream_t st )
 // Whether k_lf can read the owner's image as it is: dword-aligned base and row
 // pitch (a segment starts at the dword at or below its first pixel), byte
 // offsets in 31 bits.
-bool lfuse_takes_raw( const void* raw, int type, int ch, long stride,
-	int in_len_v, int width )
+bool lfuse_takes_raw( const ImageRef& img, int in_len_v, int width )
 {
-	const long esz = ( type == AVIRHIP_U8 ? 1 : ( type == AVIRHIP_U16 ? 2 : 4 ));
-	const long bytes = ( (long) ( in_len_v - 1 ) * stride + (long) width * ch ) * esz;
+	const long esz = (long) dtype_size( img.type );
 
-	return( raw != nullptr && ( (uintptr_t) raw & 3 ) == 0 &&
-		(( stride * esz ) & 3 ) == 0 && bytes >= 4 && bytes <= 0x7ffffffcL &&
-		ch >= 1 && ch <= 4 && esz * ch < 16 );
+	return( img.ptr != nullptr && ( (uintptr_t) img.ptr & 3 ) == 0 &&
+		(( img.stride * esz ) & 3 ) == 0 &&
+		image_dma_bytes( img, in_len_v, width ) != 0 &&
+		img.ch >= 1 && img.ch <= 4 && esz * img.ch < 16 );
 }
 
 } // namespace avirhip

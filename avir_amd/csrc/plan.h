@@ -319,6 +319,25 @@ struct PlanHold
 };
 
 size_t dtype_size( int t );
+
+// The bytes a kernel addresses behind `img` when its rows travel as bytes
+// (LDS-DMA: the range check's num_records, an int): `rows` rows at the image's
+// pitch, the last one ending with its `width` pixels, rounded up to whole dwords
+// (base and pitch are dword-aligned and device allocations dword-granular, so a
+// row's last partial dword is fetched whichever way the range check treats a
+// dword that straddles the end). 0: no such range -- under a dword, or over
+// 0x7ffffffc. (api.cpp's image_bytes is the unrounded size_t of a plan's own
+// images, for staging buffers and overlap tests: it stays what it is.)
+inline int image_dma_bytes( const ImageRef& img, const int rows,
+	const int width )
+{
+	const long bytes = ( (long) ( rows - 1 ) * img.stride +
+		(long) width * img.ch ) * (long) dtype_size( img.type );
+
+	return( bytes >= 4 && bytes <= 0x7ffffffcL ? (int) (( bytes + 3 ) & ~3L ) :
+		0 );
+}
+
 int finalize_avir_plan( avirhip_plan* p ); // api.cpp
 // device bytes a plan holds, with its inner plan, same-device spares and
 // other-device replicas (the plan caches' byte bound)

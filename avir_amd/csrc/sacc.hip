@@ -2103,16 +2103,21 @@ static void sa_launch1( const SAParams& P, int ch, int items, size_t lds,
 
 // One pass. src_type / src_ch: AVIRHIP_F32 with 4 channels goes by LDS-DMA
 // (16-byte aligned base and strides required: returns 1 otherwise); U8, U16
-// and narrower floats are read as they are. Strides in bytes (source) and
-// floats (destination); `rows`: the lanes are image rows (horizontal pass) --
-// integer sources only come so; `live_ch`: channels of the float RGBA source
-// that carry data (the others are zero padding and come out as zeros).
-int sacc_run_axis( const SAData* D, bool rows, const void* src, int src_type,
-	int src_ch, int live_ch, long s_lane, long s_step, float* dst, long d_lane,
-	long d_step, int lane_lo, int lane_hi, int out_lo, int out_hi,
-	hipStream_t st, const GPOut* out, bool finite, bool ladder,
-	bool must_two, unsigned int* flag_set, const unsigned int* guard )
+// and narrower floats are read as they are, and only come as row lanes. Every
+// refusal (1) comes before the launch.
+int sacc_run_axis( const SAData* D, const SAPass& G, const SAForm& F,
+	hipStream_t st )
 {
+	const bool rows = G.rows;
+	const void* const src = G.src;
+	const int src_type = G.src_type, src_ch = G.src_ch, live_ch = G.live_ch;
+	const long s_lane = G.s_lane, s_step = G.s_step;
+	float* const dst = G.dst;
+	const long d_lane = G.d_lane, d_step = G.d_step;
+	const int lane_lo = G.lane_lo, lane_hi = G.lane_hi;
+	const int out_lo = G.out_lo, out_hi = G.out_hi;
+	const GPOut* const out = G.out;
+
 	if( lane_hi <= lane_lo || out_hi <= out_lo )
 	{
 		return( AVIRHIP_OK );
@@ -2160,7 +2165,7 @@ int sacc_run_axis( const SAData* D, bool rows, const void* src, int src_type,
 	// lanes) or the FltBuf made from one (column lanes)
 	// (float sources come here optimistically, see SAParams::flag_set: row
 	// lanes read pixels of src_ch floats as they lie, s_step == src_ch * 4)
-	const bool two = ( finite && !ladder && D -> a.tab2 != nullptr &&
+	const bool two = ( F.finite && !F.ladder && D -> a.tab2 != nullptr &&
 		P.ax.in_len >= 8 && (( rows && out == nullptr &&
 		(( !dma && ( src_type == AVIRHIP_U8 || src_type == AVIRHIP_U16 )) ||
 		( src_type == AVIRHIP_F32 && s_step == (long) src_ch * 4 &&
@@ -2169,14 +2174,15 @@ int sacc_run_axis( const SAData* D, bool rows, const void* src, int src_type,
 		( !rows && dma && s_lane == 16 &&
 		(double) s_step * P.ax.in_len < 2147483648.0 )));
 
-	if( must_two && !two )
+	if( F.must_two && !two )
 	{
 		return( 1 );
 	}
 
-	P.flag_set = ( two && !rows ? flag_set : nullptr );
-	P.flag_clear = ( two && rows ? flag_set : nullptr );
-	P.guard = ( two ? nullptr : guard );
+	// (a null alarm pointer: the kernels raise, lower and wait for nothing)
+	P.flag_set = ( two && !rows ? F.alarm_set : nullptr );
+	P.flag_clear = ( two && rows ? F.alarm_set : nullptr );
+	P.guard = ( two ? nullptr : F.alarm_guard );
 
 	const size_t lds = ( two ? ( rows && src_type != AVIRHIP_F32 ? 0 :
 		SA2V_RING * 1024 ) :
