@@ -1099,8 +1099,10 @@ int fused_run( avirhip_plan* p, int mode, const void* src, int src_type,
 		b = ib;
 	}
 
-	a = std::max( a, 0 );
-	b = std::min( b, p -> src_h - 1 );
+	// (a band that lies off the frame reads the first or the last row alone:
+	// both ends are clamped, the range never comes out empty)
+	a = std::max( 0, std::min( a, p -> src_h - 1 ));
+	b = std::max( 0, std::min( b, p -> src_h - 1 ));
 
 	if( F -> fltbuf == nullptr )
 	{

@@ -1472,8 +1472,11 @@ __global__ void __launch_bounds__( 64 ) k_sacc2v( const SAParams P )
 	const int gbv = n1 - 1 - A.e + 3;
 	const int u_a = a_start[ ga ];
 	const int u_e = a_start[ gb ] + nt - 1;
-	const int ulo = max( u_a, 0 );
-	const int uhi = min( u_e, slast );
+	// (both ends inside the image: a chunk that lies off the frame reads the
+	// first or the last row alone -- min( u_e, slast ) by itself left uhi
+	// negative there, and with it the row offset of every fetch)
+	const int ulo = gp_clamp( u_a, slast );
+	const int uhi = gp_clamp( u_e, slast );
 	const int q_a = u_a >> 2;
 
 	const unsigned lds0 = (unsigned) (unsigned long) (lds_char*) smem;
