@@ -16,7 +16,7 @@ import ctypes as C
 import numpy as np
 
 from . import abi
-from .abi import AvirHipError, U8, U16, F32, F64, U32
+from .abi import AvirHipError, U8, U16, F32, F64, U32, F16
 
 __all__ = ["CImageResizer", "CImageResizerParams", "CImageResizerVars",
            "CLancIR", "CLancIRParams", "AvirHipError", "device_count"]
@@ -25,7 +25,8 @@ _NP2T = {np.dtype(np.uint8): U8, np.dtype(np.uint16): U16,
          np.dtype(np.float32): F32, np.dtype(np.float64): F64,
          # CLancIR only ("treated as uint16_t", lancir.h:376-377); CImageResizer
          # refuses it like the reference's unsupported types
-         np.dtype(np.uint32): U32}
+         np.dtype(np.uint32): U32,
+         np.dtype(np.float16): F16}
 
 
 def device_count():
@@ -74,7 +75,8 @@ def _buf(x):
     """-> (pointer, mem kind, dtype code, stream)"""
     if _is_torch(x):
         import torch
-        tmap = {torch.uint8: U8, torch.float32: F32, torch.float64: F64}
+        tmap = {torch.uint8: U8, torch.float32: F32, torch.float64: F64,
+                torch.float16: F16}
         if hasattr(torch, "uint16"):
             tmap[torch.uint16] = U16
         if hasattr(torch, "uint32"):

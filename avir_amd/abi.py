@@ -13,6 +13,9 @@ LIB_PATH = os.environ.get("AVIRHIP_LIB") or os.path.join(
 
 U8, U16, F32, F64 = 0, 1, 2, 3
 U32 = 4  # CLancIR only: 32-bit elements, uint16 value range (lancir.h:376-377)
+# IEEE half elements: the float32 call with the source widened exactly and the
+# float result narrowed nearest-even (include/avirhip.h, AVIRHIP_F16)
+F16 = 5
 EINVAL, ENODEV, EHIP, EUNSUPPORTED, ENOMEM, EINTERNAL = -1, -2, -3, -4, -5, -6
 MEM_HOST, MEM_DEVICE = 0, 1
 
@@ -25,6 +28,7 @@ PATH_GPASS = 5
 VARIANT_UP2_PLAIN_V, VARIANT_DN_TWO_PASS, VARIANT_SACC_LADDER = 1, 2, 4
 VARIANT_UPG_TWO_PASS, VARIANT_UPG_FUSED = 8, 16
 VARIANT_SACC_OPTIMISTIC = 32
+VARIANT_UP2_UNFUSED_IO = 64
 FPCLASS_DOUBLE = 64  # avirhip_resizer_set_fpclass: fpclass_def<double>
 
 _fp = C.POINTER(C.c_float)

@@ -39,7 +39,7 @@ void clear_error()
 size_t dtype_size( int t )
 {
 	return( t == AVIRHIP_U8 ? 1 : t == AVIRHIP_U16 ? 2 : t == AVIRHIP_F32 ? 4 :
-		t == AVIRHIP_U32 ? 4 : 8 );
+		t == AVIRHIP_U32 ? 4 : t == AVIRHIP_F16 ? 2 : 8 );
 }
 
 int guard_fail( const char* fn ) noexcept
@@ -913,9 +913,9 @@ static int lancir_owner( avirhip_plan* p, const void* src, void* dst,
 		return( AVIRHIP_OK );
 	}
 
-	// (double and uint32 elements, lancir.h:373-377: the pack pass and the
-	// output stage convert them; the fast kernels' own loaders and fused
-	// stores know uint8, uint16 and float)
+	// (double and uint32 elements, lancir.h:373-377, and half elements: the
+	// pack pass and the output stage convert them; the fast kernels' own
+	// loaders and fused stores know uint8, uint16 and float)
 	const bool in_fast = ( p -> in_type <= AVIRHIP_F32 );
 	const bool out_fast = ( p -> out_type <= AVIRHIP_F32 );
 	const ImageRef img = { src, p -> in_type, p -> io_ch, p -> src_stride };
@@ -1079,13 +1079,22 @@ static int avir_fast( avirhip_plan* p, const int path, AvirSrc& S, void* dst,
 		p -> in_type == AVIRHIP_U16 );
 	const bool int_out = ( p -> out_type == AVIRHIP_U8 ||
 		p -> out_type == AVIRHIP_U16 );
+	// (AVIRHIP_VARIANT_UP2_UNFUSED_IO: the process-wide switch, per plan)
+	const bool fio = ( fused_io() && !( path == 4 &&
+		( p -> variant & AVIRHIP_VARIANT_UP2_UNFUSED_IO )));
 
 	// integer / narrow output without gamma / error diffusion: the last pass
 	// may convert and store into the caller's image itself (no float result,
 	// no epilogue pass)
+	// (half pixels: the marching kernel alone narrows and stores them; behind
+	// every other path the output stage does)
 	const bool stores = ( !direct && !p -> gamma &&
 		(( p -> dither == AVIRHIP_DITHER_DEF && int_out ) ||
-		p -> out_type == AVIRHIP_F32 ) && fused_io());
+		p -> out_type == AVIRHIP_F32 ||
+		( p -> out_type == AVIRHIP_F16 && path == 4 )) && fio );
+	// half RGBA on both sides: the marching kernel reads the halves as they lie
+	const bool half_io = ( p -> in_type == AVIRHIP_F16 &&
+		p -> out_type == AVIRHIP_F16 && p -> io_ch == 4 );
 
 	// integer / narrower sources: the path's first kernel reads the caller's
 	// image as it lies, the float copy of the source (pack pass) is skipped --
@@ -1095,9 +1104,9 @@ static int avir_fast( avirhip_plan* p, const int path, AvirSrc& S, void* dst,
 	const bool raw = ( !p -> gamma && p -> ch == 4 && ( path == 5 ?
 		S.need_pack && ( int_in || p -> in_type == AVIRHIP_F32 ) &&
 		gpass_takes_raw( p ) :
-		path == 4 ? S.need_pack && int_in &&
-		( p -> io_ch == 3 || p -> io_ch == 4 ) && int_out &&
-		p -> dither == AVIRHIP_DITHER_DEF && up2_stores_io( p ) && fused_io() :
+		path == 4 ? S.need_pack && (( int_in &&
+		( p -> io_ch == 3 || p -> io_ch == 4 ) && int_out ) || half_io ) &&
+		p -> dither == AVIRHIP_DITHER_DEF && up2_stores_io( p ) && fio :
 		int_in && fused_takes_raw( p, path )));
 
 	if( !raw && ( rc = avir_pack( p, S, row0, row1, st )) != 0 ) return( rc );
@@ -1202,8 +1211,9 @@ static int avir_output( avirhip_plan* p, const float* fdst, void* dst,
 
 	return( launch_epilogue( fdst, dst, p -> out_type,
 		(long) ( row1 - row0 ) * p -> new_w * p -> io_ch, p -> tr_mul,
-		p -> pk_out, ( p -> gamma && ( p -> out_type != AVIRHIP_F32 ||
-		p -> fp4 )), p -> io_ch, p -> ch, p -> alpha_index, st,
+		p -> pk_out, ( p -> gamma && (( p -> out_type != AVIRHIP_F32 &&
+		p -> out_type != AVIRHIP_F16 ) || p -> fp4 )), p -> io_ch, p -> ch,
+		p -> alpha_index, st,
 		p -> d_gthr, ( p -> dither == AVIRHIP_DITHER_DEF_RNE )));
 }
 
@@ -2191,7 +2201,7 @@ const char* avirhip_last_error( void )
 
 const char* avirhip_version( void )
 {
-	return( "avirhip 0.1 (gfx950; avir v3.1 hot path)" );
+	return( "avirhip 0.2 (gfx950; avir v3.1 hot path; float16 images)" );
 }
 
 int avirhip_plan_create( const avirhip_plan_desc* d, avirhip_plan** out )
@@ -2208,10 +2218,21 @@ try
 
 	if( d -> src_w < 1 || d -> src_h < 1 || d -> new_w < 1 || d -> new_h < 1 ||
 		d -> channels < 1 || d -> channels > 4 || d -> in_type < 0 ||
-		d -> in_type > 3 || d -> out_type < 0 || d -> out_type > 3 )
+		d -> out_type < 0 || !avir_dtype_ok( d -> in_type ) ||
+		!avir_dtype_ok( d -> out_type ))
 	{
 		set_error( "bad image geometry / types" );
 		return( AVIRHIP_EINVAL );
+	}
+
+	// half elements are defined by fpclass_def<float>'s float32 call alone
+	// (avirhip.h, AVIRHIP_F16)
+	if(( d -> in_type == AVIRHIP_F16 || d -> out_type == AVIRHIP_F16 ) &&
+		( d -> work_f64 || d -> dither == AVIRHIP_DITHER_DEF_RNE ))
+	{
+		set_error( "half elements: fpclass_def<float> only (not fpclass_float4, "
+			"not the double pipeline)" );
+		return( AVIRHIP_EUNSUPPORTED );
 	}
 
 	if( !geometry_ok( "plan_create", d -> src_w, d -> src_h,
@@ -2846,8 +2867,8 @@ try
 		return( AVIRHIP_EINVAL );
 	}
 
-	if( d -> in_type < 0 || d -> in_type > AVIRHIP_U32 || d -> out_type < 0 ||
-		d -> out_type > AVIRHIP_U32 )
+	if( d -> in_type < 0 || d -> in_type > AVIRHIP_F16 || d -> out_type < 0 ||
+		d -> out_type > AVIRHIP_F16 )
 	{
 		set_error( "LANCIR: element types are uint8, uint16, uint32 (as "
 			"uint16), float or double (lancir.h:373-381)" );
@@ -2980,7 +3001,7 @@ int avirhip_plan_set_variant( avirhip_plan* p, int variant )
 try
 {
 	avirhip::clear_error();
-	if( p == nullptr || variant < 0 || variant > 63 )
+	if( p == nullptr || variant < 0 || variant > 127 )
 	{
 		set_error( "bad variant" );
 		return( AVIRHIP_EINVAL );

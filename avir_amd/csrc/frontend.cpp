@@ -320,6 +320,18 @@ try
 		return( AVIRHIP_EINVAL );
 	}
 
+	// half elements are defined by fpclass_def<float>'s float32 call
+	// (avirhip.h, AVIRHIP_F16): fpclass_float4 de-linearises its float results
+	// in an output stage of its own, fpclass_def<double> computes other values
+	if(( in_type == AVIRHIP_F16 || out_type == AVIRHIP_F16 ) &&
+		( r -> fppack == 4 || r -> f64 ))
+	{
+		set_error( "build_desc: half elements are built for fpclass_def<float> "
+			"only (not %s)", ( r -> f64 ? "fpclass_def<double>" :
+			"fpclass_float4" ));
+		return( AVIRHIP_EUNSUPPORTED );
+	}
+
 	const avirhip_vars& V = ( vars == nullptr ? g_defvars : *vars );
 	DescStore* S = r -> planner -> build( src_w, src_h, src_scanline_size,
 		new_w, new_h, el_count_io, k, V, in_type, out_type, r -> fppack,
@@ -668,7 +680,7 @@ int avirhip_resizer_resize( avirhip_resizer* r, const void* src, int src_mem,
 try
 {
 	avirhip::clear_error();
-	if( r == nullptr || out_type < 0 || out_type > 3 )
+	if( r == nullptr || !avir_dtype_ok( out_type ))
 	{
 		set_error( "resize: bad arguments" );
 		return( AVIRHIP_EINVAL );

@@ -354,6 +354,8 @@ int launch_pack( const void* src, int in_type, float* dst, int w, int h,
 			launch_pack_px< double >( src, dst, w, h, ch, src_stride, st );
 		else if( in_type == AVIRHIP_U32 )
 			launch_pack_px< uint32_t >( src, dst, w, h, ch, src_stride, st );
+		else if( in_type == AVIRHIP_F16 ) // (widened exactly: avirhip.h)
+			launch_pack_px< _Float16 >( src, dst, w, h, ch, src_stride, st );
 		else
 			launch_pack_px< float >( src, dst, w, h, ch, src_stride, st );
 
@@ -377,6 +379,9 @@ int launch_pack( const void* src, int in_type, float* dst, int w, int h,
 	else if( in_type == AVIRHIP_U32 )
 		hipLaunchKernelGGL( k_pack< uint32_t >, grd, dim3( 256 ), 0, st,
 			(const uint32_t*) src, dst, re, h, src_stride, ch, ech );
+	else if( in_type == AVIRHIP_F16 )
+		hipLaunchKernelGGL( k_pack< _Float16 >, grd, dim3( 256 ), 0, st,
+			(const _Float16*) src, dst, re, h, src_stride, ch, ech );
 	else
 		hipLaunchKernelGGL( k_pack< float >, grd, dim3( 256 ), 0, st,
 			(const float*) src, dst, re, h, src_stride, ch, ech );
@@ -588,6 +593,9 @@ int launch_pack_gamma( const void* src, int in_type, float* dst, int w, int h,
 		else if( in_type == AVIRHIP_U16 )
 			launch_pack_gamma_px< uint16_t >( src, dst, w, h, ch, src_stride,
 				alpha_index, gm, tbl, st );
+		else if( in_type == AVIRHIP_F16 )
+			launch_pack_gamma_px< _Float16 >( src, dst, w, h, ch, src_stride,
+				alpha_index, gm, tbl, st );
 		else
 			launch_pack_gamma_px< float >( src, dst, w, h, ch, src_stride,
 				alpha_index, gm, tbl, st );
@@ -607,6 +615,10 @@ int launch_pack_gamma( const void* src, int in_type, float* dst, int w, int h,
 	else if( in_type == AVIRHIP_F64 )
 		hipLaunchKernelGGL( k_pack_gamma< double >, grd, dim3( 256 ), 0, st,
 			(const double*) src, dst, re, h, src_stride, ch, ech,
+			alpha_index, gm, tbl );
+	else if( in_type == AVIRHIP_F16 )
+		hipLaunchKernelGGL( k_pack_gamma< _Float16 >, grd, dim3( 256 ), 0, st,
+			(const _Float16*) src, dst, re, h, src_stride, ch, ech,
 			alpha_index, gm, tbl );
 	else
 		hipLaunchKernelGGL( k_pack_gamma< float >, grd, dim3( 256 ), 0, st,
@@ -730,6 +742,21 @@ __global__ void __launch_bounds__( 256 ) k_epilogue_px( const float* res,
 		*(uint32_t*) ( dst + i * 4 ) = (uint32_t) o[ 0 ] |
 			( (uint32_t) o[ 1 ] << 8 ) | ( (uint32_t) o[ 2 ] << 16 ) |
 			( (uint32_t) o[ 3 ] << 24 );
+	}
+	else
+	if constexpr( CH == 4 && std::is_same< Tout, _Float16 > :: value )
+	{
+		// half RGBA: two dwords (the destination is dword-aligned here)
+		uint16_t b[ 4 ];
+#pragma unroll
+		for( int c = 0; c < 4; c++ )
+		{
+			b[ c ] = __builtin_bit_cast( uint16_t, o[ c ]);
+		}
+
+		uint32_t* const d32 = (uint32_t*) ( dst + i * 4 );
+		d32[ 0 ] = (uint32_t) b[ 0 ] | ( (uint32_t) b[ 1 ] << 16 );
+		d32[ 1 ] = (uint32_t) b[ 2 ] | ( (uint32_t) b[ 3 ] << 16 );
 	}
 	else
 	{
@@ -1006,6 +1033,9 @@ int launch_epilogue( const float* res, void* dst, int out_type, long n,
 		else if( out_type == AVIRHIP_F64 )
 			launch_epilogue_px< double, false >( res, dst, npx, ch, use_tr,
 				trm, trmi, pk, st );
+		else if( out_type == AVIRHIP_F16 ) // (narrowed nearest-even, no clamp)
+			launch_epilogue_px< _Float16, false >( res, dst, npx, ch, use_tr,
+				trm, trmi, pk, st );
 		else
 			launch_epilogue_px< float, false >( res, dst, npx, ch, use_tr,
 				trm, trmi, pk, st );
@@ -1025,6 +1055,10 @@ int launch_epilogue( const float* res, void* dst, int out_type, long n,
 	else if( out_type == AVIRHIP_F64 )
 		hipLaunchKernelGGL(( k_epilogue< double, false > ), grd, dim3( 256 ),
 			0, st, res, (double*) dst, n, use_tr, trm, trmi, pk, gamma, ch,
+			ech, alpha_index, ogm, ( rne ? 1 : 0 ));
+	else if( out_type == AVIRHIP_F16 )
+		hipLaunchKernelGGL(( k_epilogue< _Float16, false > ), grd, dim3( 256 ),
+			0, st, res, (_Float16*) dst, n, use_tr, trm, trmi, pk, gamma, ch,
 			ech, alpha_index, ogm, ( rne ? 1 : 0 ));
 	else
 		hipLaunchKernelGGL(( k_epilogue< float, false > ), grd, dim3( 256 ),
@@ -2056,6 +2090,8 @@ int launch_lancir_generic( const avirhip_plan* p, const void* src, void* dst,
 		launch_lancir_v< double >( p, src, tmp, row0, nrows, st ); // (float) ip[ c ]
 	else if( p -> in_type == AVIRHIP_U32 )
 		launch_lancir_v< uint32_t >( p, src, tmp, row0, nrows, st );
+	else if( p -> in_type == AVIRHIP_F16 )
+		launch_lancir_v< _Float16 >( p, src, tmp, row0, nrows, st );
 	else
 		launch_lancir_v< float >( p, src, tmp, row0, nrows, st );
 
@@ -2225,6 +2261,8 @@ int launch_lancir_out_pad( const avirhip_plan* p, const float* res, void* dst,
 		launch_out_pad< uint32_t >( p, res, dst, nrows, 0, st );
 	else if( p -> out_type == AVIRHIP_F64 )
 		launch_out_pad< double >( p, res, dst, nrows, 1, st );
+	else if( p -> out_type == AVIRHIP_F16 )
+		launch_out_pad< _Float16 >( p, res, dst, nrows, 1, st );
 	else
 		launch_out_pad< float >( p, res, dst, nrows, 1, st );
 
@@ -2279,6 +2317,8 @@ int launch_lancir_out( const avirhip_plan* p, const float* res, long rstride,
 	// (double: (T) ip[ i ] or (T) ( ip[ i ] * OutMul ), the product in float,
 	// lancir.h:1786-1856)
 	else if( p -> out_type == AVIRHIP_F64 ) { LO( double, 1 ); }
+	// (half: the float result -- gain applied in float -- narrowed nearest-even)
+	else if( p -> out_type == AVIRHIP_F16 ) { LO( _Float16, 1 ); }
 	else { LO( float, 1 ); }
 
 #undef LO

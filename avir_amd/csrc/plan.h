@@ -320,6 +320,13 @@ struct PlanHold
 
 size_t dtype_size( int t );
 
+// element types of CImageResizer calls: uint8, uint16, float, double, half
+// (AVIRHIP_U32 is CLancIR's alone)
+inline bool avir_dtype_ok( const int t )
+{
+	return(( t >= AVIRHIP_U8 && t <= AVIRHIP_F64 ) || t == AVIRHIP_F16 );
+}
+
 // The bytes a kernel addresses behind `img` when its rows travel as bytes
 // (LDS-DMA: the range check's num_records, an int): `rows` rows at the image's
 // pitch, the last one ending with its `width` pixels, rounded up to whole dwords

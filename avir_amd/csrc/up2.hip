@@ -315,6 +315,9 @@ __device__ __forceinline__ void u2_setprio( const int p )
 // P.ich channels stored by the vertical phase itself (a lane holds two
 // channels of a pixel: one store per channel, lanes without one carry an
 // out-of-range offset) -- no float result, no epilogue pass over it.
+// 6: half RGBA pixels (AVIRHIP_F16: the float result narrowed nearest-even, no
+// clamp -- a float-type source's sums are not known finite or small): a lane's
+// two channels are adjacent, one dword store.
 // SRC (VT only): 0 float RGBA pixels by 16-byte LDS-DMA; 10 * element size +
 // channels (13, 14, 23, 24: RGB / RGBA uint8 / uint16) the caller's integer
 // image as it lies -- packScanline's (float) cast and zero padding
@@ -323,18 +326,23 @@ __device__ __forceinline__ void u2_setprio( const int p )
 // region of the S tile, and -- the same lane, after its wave's DMA has landed,
 // before the interval's closing barrier -- reads them back, converts and writes
 // the float pixel in place. P.src then points at bytes, P.src_ss counts bytes.
+// 100 + such a code (124: half RGBA): the elements are IEEE halves, widened
+// exactly (v_cvt_f32_f16, denormals kept) instead of cast from integers.
 template< bool VT, int IO = 0, int SRC = 0 >
 __global__ void __launch_bounds__( U2_NT )
 __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 {
 	static_assert( IO == 0 || VT, "the fused output stage lives in the VT form" );
 	static_assert( SRC == 0 || VT, "raw sources live in the VT form" );
-	constexpr int SESZ = SRC / 10;       // bytes per source element (raw)
+	constexpr bool SHALF = ( SRC >= 100 ); // raw elements are halves
+	constexpr int SESZ = ( SRC % 100 ) / 10; // bytes per source element (raw)
 	constexpr int SCH = SRC % 10;        // channels of a source pixel (raw)
+	static_assert( !SHALF || SESZ == 2, "half elements are two bytes" );
 	constexpr int PXB = ( SRC != 0 ? SESZ * SCH : 16 ); // bytes per source pixel
 	// (IO 4 / 5: uint8 / uint16 results of an INTEGER source -- finite and far
 	// inside the int range, so the stage is add, convert, integer clamp)
-	constexpr int ESZ = ( IO == 1 || IO == 4 ? 1 : ( IO == 2 || IO == 5 ? 2 : 4 ));
+	constexpr int ESZ = ( IO == 1 || IO == 4 ? 1 :
+		( IO == 2 || IO == 5 || IO == 6 ? 2 : 4 ));
 	// LDS tiles, whole pixels (16 B). The horizontal phases work on whole
 	// pixels so that every LDS access is a conflict-free 128-bit one; the
 	// vertical phase reads half pixels (8 B) of T.
@@ -504,7 +512,7 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 		asm volatile( "" : "+v"( pkA ), "+v"( pkB ), "+v"( pkC ), "+v"( pkD ),
 			"+v"( pvoff ), "+v"( dlv ));
 
-		if constexpr( IO != 0 )
+		if constexpr( IO != 0 && IO != 6 )
 		{
 			asm volatile( "" : "+v"( dlv2 ));
 		}
@@ -590,6 +598,19 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 				const unsigned lo = __builtin_amdgcn_alignbyte( d1[ k ], d0[ k ], sh );
 				f4 px;
 
+				if( SHALF )
+				{
+					const unsigned hi = d1[ k ] >> ( sh * 8 );
+					px.x = (float) __builtin_bit_cast( _Float16,
+						(unsigned short) ( lo & 0xffffu ));
+					px.y = (float) __builtin_bit_cast( _Float16,
+						(unsigned short) ( lo >> 16 ));
+					px.z = (float) __builtin_bit_cast( _Float16,
+						(unsigned short) ( hi & 0xffffu ));
+					px.w = ( SCH == 4 ? (float) __builtin_bit_cast( _Float16,
+						(unsigned short) ( hi >> 16 )) : 0.0f );
+				}
+				else
 				if( SESZ == 1 )
 				{
 					px.x = (float) ( lo & 0xffu );
@@ -1100,6 +1121,19 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 		auto store_io = [&]( const f2 v, const __amdgpu_buffer_rsrc_t rs,
 			const int soff )
 		{
+			if constexpr( IO == 6 )
+			{
+				// (plain conversions: v_cvt_f16_f32 rounds to nearest even and
+				// keeps half denormals; the pkrtz form would truncate)
+				const float v0 = v.x, v1 = v.y;
+				const unsigned h0 = __builtin_bit_cast( unsigned short,
+					(_Float16) v0 );
+				const unsigned h1 = __builtin_bit_cast( unsigned short,
+					(_Float16) v1 );
+				__builtin_amdgcn_raw_buffer_store_b32( h0 | ( h1 << 16 ), rs, dlv,
+					soff, U2_STAUX );
+			}
+			else
 			if constexpr( IO == 3 )
 			{
 				// (element by element: __builtin_bit_cast of `v.y` stored v.x)
@@ -1601,8 +1635,9 @@ void up2_release( avirhip_plan* p )
 
 // Whether the plan's marching kernel can store the caller's pixels itself
 // (up2_run's `iout`): the transposed vertical phase, default ditherer, no
-// gamma, and uint8 / uint16 without bit-depth truncation or float pixels of
-// 1-3 channels.
+// gamma, and uint8 / uint16 without bit-depth truncation, float pixels of
+// 1-3 channels or half RGBA pixels (half pixels of 1-3 channels leave through
+// the output stage).
 bool up2_stores_io( const avirhip_plan* p )
 {
 	const Up2Data* D = (const Up2Data*) p -> up2;
@@ -1613,7 +1648,8 @@ bool up2_stores_io( const avirhip_plan* p )
 		p -> pk_out == 255.0 ) ||
 		( p -> out_type == AVIRHIP_U16 && p -> tr_mul == 1.0 &&
 		p -> pk_out == 65535.0 ) ||
-		( p -> out_type == AVIRHIP_F32 && p -> io_ch < 4 )));
+		( p -> out_type == AVIRHIP_F32 && p -> io_ch < 4 ) ||
+		( p -> out_type == AVIRHIP_F16 && p -> io_ch == 4 )));
 }
 
 // The float RGBA call up2_run cannot refuse (its own checks, io == 0): a source
@@ -1655,7 +1691,9 @@ int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 			( p -> out_type == AVIRHIP_U16 && p -> tr_mul == 1.0 &&
 			p -> pk_out == 65535.0 && ( (uintptr_t) iout & 1 ) == 0 ? 2 :
 			( p -> out_type == AVIRHIP_F32 && p -> io_ch < 4 &&
-			( (uintptr_t) iout & 3 ) == 0 ? 3 : 0 )));
+			( (uintptr_t) iout & 3 ) == 0 ? 3 :
+			( p -> out_type == AVIRHIP_F16 && p -> io_ch == 4 &&
+			( (uintptr_t) iout & 3 ) == 0 ? 6 : 0 ))));
 
 		if( !vt || io == 0 || p -> dither != AVIRHIP_DITHER_DEF || p -> gamma )
 		{
@@ -1675,14 +1713,19 @@ int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 	// the integer image as it lies (k_up2< true, IO, SRC >): results of
 	// integer sources only (io 4 / 5), whole frames behind the pointer, every
 	// pixel inside two aligned dwords (uint16 RGBA: dword-aligned rows)
+	// ... or the half RGBA image, stored as half RGBA (io 6), under uint16
+	// RGBA's conditions
 	int srck = 0;
 
 	if( raw != nullptr )
 	{
+		const bool half = ( p -> in_type == AVIRHIP_F16 );
 		const int esz = ( p -> in_type == AVIRHIP_U8 ? 1 : 2 );
 		const long sb = raw_stride * esz;
 
-		if(( io != 4 && io != 5 ) || ( p -> io_ch != 3 && p -> io_ch != 4 ) ||
+		if(( half ? io != 6 || p -> io_ch != 4 : ( io != 4 && io != 5 ) ||
+			( p -> in_type != AVIRHIP_U8 && p -> in_type != AVIRHIP_U16 )) ||
+			( p -> io_ch != 3 && p -> io_ch != 4 ) ||
 			win.rows > 0 || ( (uintptr_t) raw & ( esz - 1 )) ||
 			( esz == 2 && p -> io_ch == 4 && (( (uintptr_t) raw | sb ) & 3 )) ||
 			sb >= ( 1L << 22 ) || getenv( "AVIRHIP_UP2_NO_RAW" ) != nullptr )
@@ -1690,7 +1733,7 @@ int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 			return( 1 );
 		}
 
-		srck = esz * 10 + p -> io_ch;
+		srck = ( half ? 100 : 0 ) + esz * 10 + p -> io_ch;
 		src = (const float*) raw;
 		src_stride = sb;
 	}
@@ -1725,7 +1768,7 @@ int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 	P.nstrips = ( p -> new_w + U2_TW - 1 ) / U2_TW;
 	P.ibase = iout; P.ich = p -> io_ch;
 	P.istride_b = p -> new_w * p -> io_ch * ( io == 1 || io == 4 ? 1 :
-		( io == 2 || io == 5 ? 2 : 4 ));
+		( io == 2 || io == 5 || io == 6 ? 2 : 4 ));
 
 	// Chunk heights (up2_chunks.h). A chunk of h source rows costs
 	// ( h + 18 ) / U2_RB marching steps (6 rows of preload + 12 of warm-up), so
@@ -1797,6 +1840,11 @@ int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 #define U2_RAW( IOK, SK ) hipLaunchKernelGGL(( k_up2< U2_RB == 8, \
 	U2_RB == 8 ? IOK : 0, U2_RB == 8 ? SK : 0 > ), dim3( items ), \
 	dim3( U2_NT ), ldspad, st, P )
+		if( io == 6 )
+		{
+			U2_RAW( 6, 124 );
+		}
+		else
 		if( io == 4 )
 		{
 			switch( srck )
@@ -1831,6 +1879,8 @@ int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 			case 3: hipLaunchKernelGGL(( k_up2< U2_RB == 8, U2_RB == 8 ? 3 : 0 > ),
 				dim3( items ), dim3( U2_NT ), ldspad, st, P ); break;
 			case 4: hipLaunchKernelGGL(( k_up2< U2_RB == 8, U2_RB == 8 ? 4 : 0 > ),
+				dim3( items ), dim3( U2_NT ), ldspad, st, P ); break;
+			case 6: hipLaunchKernelGGL(( k_up2< U2_RB == 8, U2_RB == 8 ? 6 : 0 > ),
 				dim3( items ), dim3( U2_NT ), ldspad, st, P ); break;
 			default: hipLaunchKernelGGL(( k_up2< U2_RB == 8, U2_RB == 8 ? 5 : 0 > ),
 				dim3( items ), dim3( U2_NT ), ldspad, st, P ); break;

@@ -200,6 +200,10 @@ template<> struct dtype_of< uint8_t > { static const int v = AVIRHIP_U8; };
 template<> struct dtype_of< uint16_t > { static const int v = AVIRHIP_U16; };
 template<> struct dtype_of< float > { static const int v = AVIRHIP_F32; };
 template<> struct dtype_of< double > { static const int v = AVIRHIP_F64; };
+#ifdef __FLT16_MANT_DIG__
+// half images (the float32 call, widened / narrowed: avirhip.h AVIRHIP_F16)
+template<> struct dtype_of< _Float16 > { static const int v = AVIRHIP_F16; };
+#endif
 
 /* Memory exhaustion comes back from the library as a code (no exception
  * crosses its C boundary) and leaves here as what the reference itself throws,

@@ -52,7 +52,21 @@ typedef enum avirhip_dtype {
 	/* CLancIR only: 32-bit unsigned elements whose value range is treated as
 	 * uint16_t's, 0..65535 (lancir.h:373-377; Clamp / OutMul derive from
 	 * sizeof() == 1 or not, lancir.h:531-533). */
-	AVIRHIP_U32 = 4
+	AVIRHIP_U32 = 4,
+	/* IEEE binary16 ("half") elements. The reference has no such type; a call
+	 * with half elements is DEFINED by the same call with float buffers.
+	 * Source: every half (denormals included) is widened exactly to float, and
+	 * the call then behaves in every respect as a float32 source does (scaling,
+	 * SrcBitDepth, gamma linearisation, channel padding). Result: the call
+	 * computes exactly the float32 result fpclass_def<float> / CLancIR would
+	 * store into a float32 destination (with UseSRGBGamma it stays linear; no
+	 * clamp, no PkOut scale, not dithered), and each element is narrowed to
+	 * half with round-to-nearest-even: half denormals are kept, values beyond
+	 * +-65504 become +-Inf, NaN stays NaN. The two sides are independent: half
+	 * mixes freely with the other types. fpclass_float4 and fpclass_def<double>
+	 * refuse half elements (AVIRHIP_EUNSUPPORTED): their float results pass
+	 * through an output stage of their own -- a different contract. */
+	AVIRHIP_F16 = 5
 } avirhip_dtype;
 
 /* Where a buffer passed to an execute call lives. */
@@ -272,6 +286,11 @@ int avirhip_plan_get_path(const avirhip_plan* plan);
  * pixels of 1-3 channels; automatically such sources take the exact kernels
  * alone, which are as fast there and need no alarm launches */
 #define AVIRHIP_VARIANT_SACC_OPTIMISTIC 32
+/* path 4: the marching kernel reads the pack pass' float copy of the source and
+ * writes a float result for the output stage, where it would read or store the
+ * caller's integer / half pixels itself (the A/B and differential form of the
+ * fused I/O; float RGBA images are the kernel's own format either way) */
+#define AVIRHIP_VARIANT_UP2_UNFUSED_IO 64
 int avirhip_plan_set_variant(avirhip_plan* plan, int variant);
 
 /* Device memory the plan holds right now, in bytes: tables, scratch buffers

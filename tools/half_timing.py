@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""What half (float16) pixels buy on the exact-2x marching kernel: cfg3
+(3840x2160 -> 7680x4320 RGBA) and cfg2 (1920x1080 -> 3840x2160) as
+  (a) float32 -> float32 (the baseline; with PARENT.so also on that build),
+  (b) half -> half, read and stored by k_up2 itself (k_up2< true, 6, 124 >),
+  (c) half -> half through the pack pass and the output stage
+      (AVIRHIP_VARIANT_UP2_UNFUSED_IO),
+  (d) float32 -> half (k_up2< true, 6 >),
+one process, avirhip_time_resize, every figure over a ring of distinct source /
+destination pairs of more than 512 MiB in all (twice the Infinity Cache), the
+rows alternating REPS times. Prints the table with the achieved bytes/s, the
+library's md5 and the device clocks.
+
+usage: python tools/half_timing.py [PARENT.so] [REPS=5]"""
+import ctypes as C
+import hashlib
+import os
+import subprocess
+import sys
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+
+
+def md5(path):
+    with open(path, "rb") as f:
+        return hashlib.md5(f.read()).hexdigest()
+
+
+def main():
+    import numpy as np
+    import torch
+    import avir_amd
+    from avir_amd import abi, synth
+    parent = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1] != "-" else None
+    reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    lib = abi.load()
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    print("library %s md5 %s" % (abi.LIB_PATH, md5(abi.LIB_PATH)))
+    print("version %s" % lib.avirhip_version().decode())
+    if parent:
+        print("parent  %s md5 %s" % (parent, md5(parent)))
+    print("device  %s" % torch.cuda.get_device_name(0))
+    try:
+        out = subprocess.run(["rocm-smi", "--showclocks", "-d", "0"],
+                             capture_output=True, text=True, timeout=60).stdout
+        for l in out.split("\n"):
+            if "sclk" in l or "mclk" in l or "fclk" in l:
+                print("clocks  " + l.strip())
+    except Exception as e:  # (the table stands without them)
+        print("clocks  unavailable: %r" % (e,))
+    TD = {abi.F32: torch.float32, abi.F16: torch.float16}
+    ES = {abi.F32: 4, abi.F16: 2}
+    for name, (sw, sh) in (("cfg3", (3840, 2160)), ("cfg2", (1920, 1080))):
+        nw, nh = 2 * sw, 2 * sh
+        base = synth.lcg_f32((sh, sw, 4))
+        rows = [("a  f32->f32", lib, abi.F32, abi.F32, 0),
+                ("b  f16->f16 fused", lib, abi.F16, abi.F16, 0),
+                ("c  f16->f16 pack + output stage", lib, abi.F16, abi.F16,
+                 abi.VARIANT_UP2_UNFUSED_IO),
+                ("d  f32->f16", lib, abi.F32, abi.F16, 0)]
+        if parent:
+            rows.insert(0, ("a' f32->f32 parent build", abi.load_path(parent),
+                            abi.F32, abi.F32, 0))
+        run, keep, first = {}, [], {}
+        for tag, L, ti, to, variant in rows:
+            pair = sw * sh * 4 * ES[ti] + nw * nh * 4 * ES[to]
+            n = max(2, -(-(512 << 20) // pair))
+            ring = []
+            for i in range(n):
+                s = torch.from_numpy(np.roll(base, i, axis=0)).to(dev).to(TD[ti])
+                d = torch.empty((nh, nw, 4), dtype=TD[to], device=dev)
+                ring.append((s, d))
+            with abi.using(L):
+                r = avir_amd.CImageResizer(16)
+                p = r.plan(sw, sh, nw, nh, 4, 0.0, None, ti, to)
+            abi.check(L.avirhip_plan_set_path(p, abi.PATH_UP2), "path 4")
+            if variant:
+                abi.check(L.avirhip_plan_set_variant(p, variant), "variant")
+            keep.append((r, ring))
+
+            def once(L=L, p=p, ring=ring):
+                t = 0.0
+                ms = C.c_double()
+                for s, d in ring:
+                    abi.check(L.avirhip_time_resize(
+                        p, s.data_ptr(), d.data_ptr(), 1, st, C.byref(ms)),
+                        "time_resize")
+                    t += ms.value
+                return t / len(ring)
+            run[tag] = (once, pair, n)
+            first[tag] = ring[0][1]
+        for tag in run:  # warm-up, clocks
+            for _ in range(20):
+                run[tag][0]()
+        torch.cuda.synchronize()
+        same = torch.equal(first["b  f16->f16 fused"].view(torch.uint8),
+                           first["c  f16->f16 pack + output stage"].view(
+                               torch.uint8))
+        res = {tag: [] for tag in run}
+        loops = 30 if name == "cfg3" else 60
+        for _ in range(reps):
+            for tag in run:
+                res[tag].append(sum(run[tag][0]() for _ in range(loops)) / loops)
+        print("%s (%dx%d -> %dx%d RGBA), ring pairs per row below, %d reps x "
+              "%d ring passes:" % (name, sw, sh, nw, nh, reps, loops))
+        for tag in run:
+            v = sorted(res[tag])
+            med = v[len(v) // 2]
+            print("  %-34s %.4f ms  (min %.4f max %.4f)  %6.1f MB/call  "
+                  "%.2f TB/s  ring %d" % (
+                      tag, med, v[0], v[-1], run[tag][1] / 1e6,
+                      run[tag][1] / med / 1e9, run[tag][2]), flush=True)
+        print("  (b) and (c) bit-identical: %s" % same, flush=True)
+        del keep, run, first
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
