@@ -16,7 +16,7 @@ import ctypes as C
 import numpy as np
 
 from . import abi
-from .abi import AvirHipError, U8, U16, F32, F64, U32, F16
+from .abi import AvirHipError, U8, U16, F32, F64, U32, F16, BF16
 
 __all__ = ["CImageResizer", "CImageResizerParams", "CImageResizerVars",
            "CLancIR", "CLancIRParams", "AvirHipError", "device_count"]
@@ -76,7 +76,7 @@ def _buf(x):
     if _is_torch(x):
         import torch
         tmap = {torch.uint8: U8, torch.float32: F32, torch.float64: F64,
-                torch.float16: F16}
+                torch.float16: F16, torch.bfloat16: BF16}
         if hasattr(torch, "uint16"):
             tmap[torch.uint16] = U16
         if hasattr(torch, "uint32"):

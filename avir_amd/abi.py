@@ -16,6 +16,9 @@ U32 = 4  # CLancIR only: 32-bit elements, uint16 value range (lancir.h:376-377)
 # IEEE half elements: the float32 call with the source widened exactly and the
 # float result narrowed nearest-even (include/avirhip.h, AVIRHIP_F16)
 F16 = 5
+# bfloat16 elements (the upper half of a float32): the same rule, widened by
+# bits << 16, narrowed nearest-even (include/avirhip.h, AVIRHIP_BF16)
+BF16 = 6
 EINVAL, ENODEV, EHIP, EUNSUPPORTED, ENOMEM, EINTERNAL = -1, -2, -3, -4, -5, -6
 MEM_HOST, MEM_DEVICE = 0, 1
 

@@ -39,7 +39,7 @@ void clear_error()
 size_t dtype_size( int t )
 {
 	return( t == AVIRHIP_U8 ? 1 : t == AVIRHIP_U16 ? 2 : t == AVIRHIP_F32 ? 4 :
-		t == AVIRHIP_U32 ? 4 : t == AVIRHIP_F16 ? 2 : 8 );
+		t == AVIRHIP_U32 ? 4 : dtype_is_float16_kind( t ) ? 2 : 8 );
 }
 
 int guard_fail( const char* fn ) noexcept
@@ -913,7 +913,7 @@ static int lancir_owner( avirhip_plan* p, const void* src, void* dst,
 		return( AVIRHIP_OK );
 	}
 
-	// (double and uint32 elements, lancir.h:373-377, and half elements: the
+	// (double and uint32 elements, lancir.h:373-377, half and bfloat16 ones: the
 	// pack pass and the output stage convert them; the fast kernels' own
 	// loaders and fused stores know uint8, uint16 and float)
 	const bool in_fast = ( p -> in_type <= AVIRHIP_F32 );
@@ -1086,15 +1086,16 @@ static int avir_fast( avirhip_plan* p, const int path, AvirSrc& S, void* dst,
 	// integer / narrow output without gamma / error diffusion: the last pass
 	// may convert and store into the caller's image itself (no float result,
 	// no epilogue pass)
-	// (half pixels: the marching kernel alone narrows and stores them; behind
-	// every other path the output stage does)
+	// (half / bfloat16 pixels: the marching kernel alone narrows and stores
+	// them; behind every other path the output stage does)
 	const bool stores = ( !direct && !p -> gamma &&
 		(( p -> dither == AVIRHIP_DITHER_DEF && int_out ) ||
 		p -> out_type == AVIRHIP_F32 ||
-		( p -> out_type == AVIRHIP_F16 && path == 4 )) && fio );
-	// half RGBA on both sides: the marching kernel reads the halves as they lie
-	const bool half_io = ( p -> in_type == AVIRHIP_F16 &&
-		p -> out_type == AVIRHIP_F16 && p -> io_ch == 4 );
+		( dtype_is_float16_kind( p -> out_type ) && path == 4 )) && fio );
+	// half RGBA on both sides, or bfloat16 RGBA on both sides: the marching
+	// kernel reads the elements as they lie
+	const bool half_io = ( dtype_is_float16_kind( p -> in_type ) &&
+		p -> out_type == p -> in_type && p -> io_ch == 4 );
 
 	// integer / narrower sources: the path's first kernel reads the caller's
 	// image as it lies, the float copy of the source (pack pass) is skipped --
@@ -1212,8 +1213,8 @@ static int avir_output( avirhip_plan* p, const float* fdst, void* dst,
 	return( launch_epilogue( fdst, dst, p -> out_type,
 		(long) ( row1 - row0 ) * p -> new_w * p -> io_ch, p -> tr_mul,
 		p -> pk_out, ( p -> gamma && (( p -> out_type != AVIRHIP_F32 &&
-		p -> out_type != AVIRHIP_F16 ) || p -> fp4 )), p -> io_ch, p -> ch,
-		p -> alpha_index, st,
+		!dtype_is_float16_kind( p -> out_type )) || p -> fp4 )), p -> io_ch,
+		p -> ch, p -> alpha_index, st,
 		p -> d_gthr, ( p -> dither == AVIRHIP_DITHER_DEF_RNE )));
 }
 
@@ -2225,13 +2226,14 @@ try
 		return( AVIRHIP_EINVAL );
 	}
 
-	// half elements are defined by fpclass_def<float>'s float32 call alone
-	// (avirhip.h, AVIRHIP_F16)
-	if(( d -> in_type == AVIRHIP_F16 || d -> out_type == AVIRHIP_F16 ) &&
+	// half / bfloat16 elements are defined by fpclass_def<float>'s float32
+	// call alone (avirhip.h, AVIRHIP_F16 / AVIRHIP_BF16)
+	if(( dtype_is_float16_kind( d -> in_type ) ||
+		dtype_is_float16_kind( d -> out_type )) &&
 		( d -> work_f64 || d -> dither == AVIRHIP_DITHER_DEF_RNE ))
 	{
-		set_error( "half elements: fpclass_def<float> only (not fpclass_float4, "
-			"not the double pipeline)" );
+		set_error( "half / bfloat16 elements: fpclass_def<float> only (not "
+			"fpclass_float4, not the double pipeline)" );
 		return( AVIRHIP_EUNSUPPORTED );
 	}
 
@@ -2867,8 +2869,8 @@ try
 		return( AVIRHIP_EINVAL );
 	}
 
-	if( d -> in_type < 0 || d -> in_type > AVIRHIP_F16 || d -> out_type < 0 ||
-		d -> out_type > AVIRHIP_F16 )
+	if( d -> in_type < 0 || d -> in_type > AVIRHIP_BF16 || d -> out_type < 0 ||
+		d -> out_type > AVIRHIP_BF16 )
 	{
 		set_error( "LANCIR: element types are uint8, uint16, uint32 (as "
 			"uint16), float or double (lancir.h:373-381)" );

@@ -320,15 +320,16 @@ try
 		return( AVIRHIP_EINVAL );
 	}
 
-	// half elements are defined by fpclass_def<float>'s float32 call
-	// (avirhip.h, AVIRHIP_F16): fpclass_float4 de-linearises its float results
-	// in an output stage of its own, fpclass_def<double> computes other values
-	if(( in_type == AVIRHIP_F16 || out_type == AVIRHIP_F16 ) &&
-		( r -> fppack == 4 || r -> f64 ))
+	// half / bfloat16 elements are defined by fpclass_def<float>'s float32 call
+	// (avirhip.h, AVIRHIP_F16 / AVIRHIP_BF16): fpclass_float4 de-linearises its
+	// float results in an output stage of its own, fpclass_def<double> computes
+	// other values
+	if(( dtype_is_float16_kind( in_type ) ||
+		dtype_is_float16_kind( out_type )) && ( r -> fppack == 4 || r -> f64 ))
 	{
-		set_error( "build_desc: half elements are built for fpclass_def<float> "
-			"only (not %s)", ( r -> f64 ? "fpclass_def<double>" :
-			"fpclass_float4" ));
+		set_error( "build_desc: half / bfloat16 elements are built for "
+			"fpclass_def<float> only (not %s)", ( r -> f64 ?
+			"fpclass_def<double>" : "fpclass_float4" ));
 		return( AVIRHIP_EUNSUPPORTED );
 	}
 

@@ -356,6 +356,8 @@ int launch_pack( const void* src, int in_type, float* dst, int w, int h,
 			launch_pack_px< uint32_t >( src, dst, w, h, ch, src_stride, st );
 		else if( in_type == AVIRHIP_F16 ) // (widened exactly: avirhip.h)
 			launch_pack_px< _Float16 >( src, dst, w, h, ch, src_stride, st );
+		else if( in_type == AVIRHIP_BF16 ) // (bits << 16)
+			launch_pack_px< __bf16 >( src, dst, w, h, ch, src_stride, st );
 		else
 			launch_pack_px< float >( src, dst, w, h, ch, src_stride, st );
 
@@ -382,6 +384,9 @@ int launch_pack( const void* src, int in_type, float* dst, int w, int h,
 	else if( in_type == AVIRHIP_F16 )
 		hipLaunchKernelGGL( k_pack< _Float16 >, grd, dim3( 256 ), 0, st,
 			(const _Float16*) src, dst, re, h, src_stride, ch, ech );
+	else if( in_type == AVIRHIP_BF16 )
+		hipLaunchKernelGGL( k_pack< __bf16 >, grd, dim3( 256 ), 0, st,
+			(const __bf16*) src, dst, re, h, src_stride, ch, ech );
 	else
 		hipLaunchKernelGGL( k_pack< float >, grd, dim3( 256 ), 0, st,
 			(const float*) src, dst, re, h, src_stride, ch, ech );
@@ -596,6 +601,9 @@ int launch_pack_gamma( const void* src, int in_type, float* dst, int w, int h,
 		else if( in_type == AVIRHIP_F16 )
 			launch_pack_gamma_px< _Float16 >( src, dst, w, h, ch, src_stride,
 				alpha_index, gm, tbl, st );
+		else if( in_type == AVIRHIP_BF16 )
+			launch_pack_gamma_px< __bf16 >( src, dst, w, h, ch, src_stride,
+				alpha_index, gm, tbl, st );
 		else
 			launch_pack_gamma_px< float >( src, dst, w, h, ch, src_stride,
 				alpha_index, gm, tbl, st );
@@ -619,6 +627,10 @@ int launch_pack_gamma( const void* src, int in_type, float* dst, int w, int h,
 	else if( in_type == AVIRHIP_F16 )
 		hipLaunchKernelGGL( k_pack_gamma< _Float16 >, grd, dim3( 256 ), 0, st,
 			(const _Float16*) src, dst, re, h, src_stride, ch, ech,
+			alpha_index, gm, tbl );
+	else if( in_type == AVIRHIP_BF16 )
+		hipLaunchKernelGGL( k_pack_gamma< __bf16 >, grd, dim3( 256 ), 0, st,
+			(const __bf16*) src, dst, re, h, src_stride, ch, ech,
 			alpha_index, gm, tbl );
 	else
 		hipLaunchKernelGGL( k_pack_gamma< float >, grd, dim3( 256 ), 0, st,
@@ -744,9 +756,10 @@ __global__ void __launch_bounds__( 256 ) k_epilogue_px( const float* res,
 			( (uint32_t) o[ 3 ] << 24 );
 	}
 	else
-	if constexpr( CH == 4 && std::is_same< Tout, _Float16 > :: value )
+	if constexpr( CH == 4 && ( std::is_same< Tout, _Float16 > :: value ||
+		std::is_same< Tout, __bf16 > :: value ))
 	{
-		// half RGBA: two dwords (the destination is dword-aligned here)
+		// half / bfloat16 RGBA: two dwords (the destination is dword-aligned here)
 		uint16_t b[ 4 ];
 #pragma unroll
 		for( int c = 0; c < 4; c++ )
@@ -1036,6 +1049,9 @@ int launch_epilogue( const float* res, void* dst, int out_type, long n,
 		else if( out_type == AVIRHIP_F16 ) // (narrowed nearest-even, no clamp)
 			launch_epilogue_px< _Float16, false >( res, dst, npx, ch, use_tr,
 				trm, trmi, pk, st );
+		else if( out_type == AVIRHIP_BF16 ) // (the same, avirhip.h)
+			launch_epilogue_px< __bf16, false >( res, dst, npx, ch, use_tr,
+				trm, trmi, pk, st );
 		else
 			launch_epilogue_px< float, false >( res, dst, npx, ch, use_tr,
 				trm, trmi, pk, st );
@@ -1059,6 +1075,10 @@ int launch_epilogue( const float* res, void* dst, int out_type, long n,
 	else if( out_type == AVIRHIP_F16 )
 		hipLaunchKernelGGL(( k_epilogue< _Float16, false > ), grd, dim3( 256 ),
 			0, st, res, (_Float16*) dst, n, use_tr, trm, trmi, pk, gamma, ch,
+			ech, alpha_index, ogm, ( rne ? 1 : 0 ));
+	else if( out_type == AVIRHIP_BF16 )
+		hipLaunchKernelGGL(( k_epilogue< __bf16, false > ), grd, dim3( 256 ),
+			0, st, res, (__bf16*) dst, n, use_tr, trm, trmi, pk, gamma, ch,
 			ech, alpha_index, ogm, ( rne ? 1 : 0 ));
 	else
 		hipLaunchKernelGGL(( k_epilogue< float, false > ), grd, dim3( 256 ),
@@ -2092,6 +2112,8 @@ int launch_lancir_generic( const avirhip_plan* p, const void* src, void* dst,
 		launch_lancir_v< uint32_t >( p, src, tmp, row0, nrows, st );
 	else if( p -> in_type == AVIRHIP_F16 )
 		launch_lancir_v< _Float16 >( p, src, tmp, row0, nrows, st );
+	else if( p -> in_type == AVIRHIP_BF16 )
+		launch_lancir_v< __bf16 >( p, src, tmp, row0, nrows, st );
 	else
 		launch_lancir_v< float >( p, src, tmp, row0, nrows, st );
 
@@ -2263,6 +2285,8 @@ int launch_lancir_out_pad( const avirhip_plan* p, const float* res, void* dst,
 		launch_out_pad< double >( p, res, dst, nrows, 1, st );
 	else if( p -> out_type == AVIRHIP_F16 )
 		launch_out_pad< _Float16 >( p, res, dst, nrows, 1, st );
+	else if( p -> out_type == AVIRHIP_BF16 )
+		launch_out_pad< __bf16 >( p, res, dst, nrows, 1, st );
 	else
 		launch_out_pad< float >( p, res, dst, nrows, 1, st );
 
@@ -2319,6 +2343,7 @@ int launch_lancir_out( const avirhip_plan* p, const float* res, long rstride,
 	else if( p -> out_type == AVIRHIP_F64 ) { LO( double, 1 ); }
 	// (half: the float result -- gain applied in float -- narrowed nearest-even)
 	else if( p -> out_type == AVIRHIP_F16 ) { LO( _Float16, 1 ); }
+	else if( p -> out_type == AVIRHIP_BF16 ) { LO( __bf16, 1 ); }
 	else { LO( float, 1 ); }
 
 #undef LO

@@ -1391,7 +1391,7 @@ bool gpass_takes_raw( const avirhip_plan* p )
 		p -> in_type == AVIRHIP_U16 );
 
 	// (the loaders know uint8, uint16 and float elements: any other type --
-	// half, double -- goes through the pack pass)
+	// half, bfloat16, double -- goes through the pack pass)
 	return( D != nullptr && !p -> is_lancir &&
 		( int_src || p -> in_type == AVIRHIP_F32 ) &&
 		( sa_wanted( D -> sa_h, int_src || ( p -> in_type == AVIRHIP_F32 &&

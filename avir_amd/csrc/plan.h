@@ -320,11 +320,19 @@ struct PlanHold
 
 size_t dtype_size( int t );
 
-// element types of CImageResizer calls: uint8, uint16, float, double, half
-// (AVIRHIP_U32 is CLancIR's alone)
+// element types of CImageResizer calls: uint8, uint16, float, double, half,
+// bfloat16 (AVIRHIP_U32 is CLancIR's alone)
 inline bool avir_dtype_ok( const int t )
 {
-	return(( t >= AVIRHIP_U8 && t <= AVIRHIP_F64 ) || t == AVIRHIP_F16 );
+	return(( t >= AVIRHIP_U8 && t <= AVIRHIP_F64 ) || t == AVIRHIP_F16 ||
+		t == AVIRHIP_BF16 );
+}
+
+// the 16-bit float types: defined by the float32 call (avirhip.h), planned as
+// float32, converted by the pack pass / the output stage or by k_up2 itself
+inline bool dtype_is_float16_kind( const int t )
+{
+	return( t == AVIRHIP_F16 || t == AVIRHIP_BF16 );
 }
 
 // The bytes a kernel addresses behind `img` when its rows travel as bytes

@@ -664,8 +664,8 @@ DescStore* lancir_build( int sw, int sh, int nw, int nh, int ch,
 	const avirhip_lancir_params& P, int in_type, int out_type )
 {
 	if( sw < 1 || sh < 1 || nw < 1 || nh < 1 || ch < 1 || ch > 4 ||
-		P.la < 2.0 || in_type < 0 || in_type > AVIRHIP_F16 || out_type < 0 ||
-		out_type > AVIRHIP_F16 )
+		P.la < 2.0 || in_type < 0 || in_type > AVIRHIP_BF16 || out_type < 0 ||
+		out_type > AVIRHIP_BF16 )
 	{
 		set_error( "lancir planner: bad arguments" );
 		return( nullptr );
@@ -724,13 +724,14 @@ DescStore* lancir_build( int sw, int sh, int nw, int nh, int ch,
 	// uint16_t" (lancir.h:373-381) -- what the reference derives from the types
 	// is IsInFloat / IsOutFloat and sizeof() (a uint32_t is a non-float of size
 	// 4: range 65535, but never "the same size" as a uint16_t)
-	// (a half image is defined by the float image it widens to / narrows from,
-	// avirhip.h AVIRHIP_F16: it plans as float32 in every respect)
+	// (a half / bfloat16 image is defined by the float image it widens to /
+	// narrows from, avirhip.h AVIRHIP_F16 / AVIRHIP_BF16: it plans as float32
+	// in every respect)
 	const bool inFloat = ( in_type == AVIRHIP_F32 || in_type == AVIRHIP_F64 ||
-		in_type == AVIRHIP_F16 );
+		in_type == AVIRHIP_F16 || in_type == AVIRHIP_BF16 );
 	const bool outFloat = ( out_type == AVIRHIP_F32 || out_type == AVIRHIP_F64 ||
-		out_type == AVIRHIP_F16 );
-	static const int tsz[ 6 ] = { 1, 2, 4, 8, 4, 4 };
+		out_type == AVIRHIP_F16 || out_type == AVIRHIP_BF16 );
+	static const int tsz[ 7 ] = { 1, 2, 4, 8, 4, 4, 4 };
 	const int szin = tsz[ in_type ];
 	const int szout = tsz[ out_type ];
 	d.is_unity_mul = (( inFloat && outFloat ) ||

@@ -1088,8 +1088,10 @@ DescStore* build_impl( AvirPlannerImpl& I, int sw, int sh, int sstride, int nw,
 	int out_type, int fppack )
 {
 	if( sw < 1 || sh < 1 || nw < 1 || nh < 1 || ch < 1 || ch > 4 ||
-		in_type < 0 || ( in_type > 3 && in_type != AVIRHIP_F16 ) ||
-		out_type < 0 || ( out_type > 3 && out_type != AVIRHIP_F16 ))
+		in_type < 0 || ( in_type > 3 && in_type != AVIRHIP_F16 &&
+		in_type != AVIRHIP_BF16 ) ||
+		out_type < 0 || ( out_type > 3 && out_type != AVIRHIP_F16 &&
+		out_type != AVIRHIP_BF16 ))
 	{
 		set_error( "planner: bad geometry / types" );
 		return( nullptr );

@@ -318,6 +318,8 @@ __device__ __forceinline__ void u2_setprio( const int p )
 // 6: half RGBA pixels (AVIRHIP_F16: the float result narrowed nearest-even, no
 // clamp -- a float-type source's sums are not known finite or small): a lane's
 // two channels are adjacent, one dword store.
+// 7: bfloat16 RGBA pixels (AVIRHIP_BF16) the same way: the two floats narrowed
+// nearest-even (the (__bf16) cast: v_cvt_pk_bf16_f32 on gfx950), one dword.
 // SRC (VT only): 0 float RGBA pixels by 16-byte LDS-DMA; 10 * element size +
 // channels (13, 14, 23, 24: RGB / RGBA uint8 / uint16) the caller's integer
 // image as it lies -- packScanline's (float) cast and zero padding
@@ -328,21 +330,25 @@ __device__ __forceinline__ void u2_setprio( const int p )
 // the float pixel in place. P.src then points at bytes, P.src_ss counts bytes.
 // 100 + such a code (124: half RGBA): the elements are IEEE halves, widened
 // exactly (v_cvt_f32_f16, denormals kept) instead of cast from integers.
+// 200 + such a code (224: bfloat16 RGBA): the elements are upper halves of
+// floats -- a shift and a mask per dword, no conversion.
 template< bool VT, int IO = 0, int SRC = 0 >
 __global__ void __launch_bounds__( U2_NT )
 __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 {
 	static_assert( IO == 0 || VT, "the fused output stage lives in the VT form" );
 	static_assert( SRC == 0 || VT, "raw sources live in the VT form" );
-	constexpr bool SHALF = ( SRC >= 100 ); // raw elements are halves
+	constexpr bool SHALF = ( SRC / 100 == 1 ); // raw elements are halves
+	constexpr bool SBF16 = ( SRC / 100 == 2 ); // raw elements are bfloat16s
 	constexpr int SESZ = ( SRC % 100 ) / 10; // bytes per source element (raw)
 	constexpr int SCH = SRC % 10;        // channels of a source pixel (raw)
-	static_assert( !SHALF || SESZ == 2, "half elements are two bytes" );
+	static_assert( !( SHALF || SBF16 ) || SESZ == 2,
+		"half / bfloat16 elements are two bytes" );
 	constexpr int PXB = ( SRC != 0 ? SESZ * SCH : 16 ); // bytes per source pixel
 	// (IO 4 / 5: uint8 / uint16 results of an INTEGER source -- finite and far
 	// inside the int range, so the stage is add, convert, integer clamp)
 	constexpr int ESZ = ( IO == 1 || IO == 4 ? 1 :
-		( IO == 2 || IO == 5 || IO == 6 ? 2 : 4 ));
+		( IO == 2 || IO == 5 || IO == 6 || IO == 7 ? 2 : 4 ));
 	// LDS tiles, whole pixels (16 B). The horizontal phases work on whole
 	// pixels so that every LDS access is a conflict-free 128-bit one; the
 	// vertical phase reads half pixels (8 B) of T.
@@ -512,7 +518,7 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 		asm volatile( "" : "+v"( pkA ), "+v"( pkB ), "+v"( pkC ), "+v"( pkD ),
 			"+v"( pvoff ), "+v"( dlv ));
 
-		if constexpr( IO != 0 && IO != 6 )
+		if constexpr( IO != 0 && IO != 6 && IO != 7 )
 		{
 			asm volatile( "" : "+v"( dlv2 ));
 		}
@@ -598,6 +604,17 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 				const unsigned lo = __builtin_amdgcn_alignbyte( d1[ k ], d0[ k ], sh );
 				f4 px;
 
+				if( SBF16 )
+				{
+					// (exact for every bit pattern: the element is the float's
+					// upper half)
+					const unsigned hi = d1[ k ] >> ( sh * 8 );
+					px.x = __uint_as_float( lo << 16 );
+					px.y = __uint_as_float( lo & 0xffff0000u );
+					px.z = __uint_as_float( hi << 16 );
+					px.w = ( SCH == 4 ? __uint_as_float( hi & 0xffff0000u ) : 0.0f );
+				}
+				else
 				if( SHALF )
 				{
 					const unsigned hi = d1[ k ] >> ( sh * 8 );
@@ -1121,6 +1138,17 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 		auto store_io = [&]( const f2 v, const __amdgpu_buffer_rsrc_t rs,
 			const int soff )
 		{
+			if constexpr( IO == 7 )
+			{
+				// (a plain conversion of the pair, ONE v_cvt_pk_bf16_f32: nearest
+				// even, float denormals become bfloat16 denormals, beyond the
+				// largest finite one +-Inf)
+				typedef __bf16 bf2 __attribute__(( ext_vector_type( 2 )));
+				__builtin_amdgcn_raw_buffer_store_b32( __builtin_bit_cast(
+					unsigned, __builtin_convertvector( v, bf2 )), rs, dlv, soff,
+					U2_STAUX );
+			}
+			else
 			if constexpr( IO == 6 )
 			{
 				// (plain conversions: v_cvt_f16_f32 rounds to nearest even and
@@ -1636,8 +1664,8 @@ void up2_release( avirhip_plan* p )
 // Whether the plan's marching kernel can store the caller's pixels itself
 // (up2_run's `iout`): the transposed vertical phase, default ditherer, no
 // gamma, and uint8 / uint16 without bit-depth truncation, float pixels of
-// 1-3 channels or half RGBA pixels (half pixels of 1-3 channels leave through
-// the output stage).
+// 1-3 channels or half / bfloat16 RGBA pixels (such pixels of 1-3 channels
+// leave through the output stage).
 bool up2_stores_io( const avirhip_plan* p )
 {
 	const Up2Data* D = (const Up2Data*) p -> up2;
@@ -1649,7 +1677,7 @@ bool up2_stores_io( const avirhip_plan* p )
 		( p -> out_type == AVIRHIP_U16 && p -> tr_mul == 1.0 &&
 		p -> pk_out == 65535.0 ) ||
 		( p -> out_type == AVIRHIP_F32 && p -> io_ch < 4 ) ||
-		( p -> out_type == AVIRHIP_F16 && p -> io_ch == 4 )));
+		( dtype_is_float16_kind( p -> out_type ) && p -> io_ch == 4 )));
 }
 
 // The float RGBA call up2_run cannot refuse (its own checks, io == 0): a source
@@ -1693,7 +1721,9 @@ int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 			( p -> out_type == AVIRHIP_F32 && p -> io_ch < 4 &&
 			( (uintptr_t) iout & 3 ) == 0 ? 3 :
 			( p -> out_type == AVIRHIP_F16 && p -> io_ch == 4 &&
-			( (uintptr_t) iout & 3 ) == 0 ? 6 : 0 ))));
+			( (uintptr_t) iout & 3 ) == 0 ? 6 :
+			( p -> out_type == AVIRHIP_BF16 && p -> io_ch == 4 &&
+			( (uintptr_t) iout & 3 ) == 0 ? 7 : 0 )))));
 
 		if( !vt || io == 0 || p -> dither != AVIRHIP_DITHER_DEF || p -> gamma )
 		{
@@ -1713,17 +1743,20 @@ int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 	// the integer image as it lies (k_up2< true, IO, SRC >): results of
 	// integer sources only (io 4 / 5), whole frames behind the pointer, every
 	// pixel inside two aligned dwords (uint16 RGBA: dword-aligned rows)
-	// ... or the half RGBA image, stored as half RGBA (io 6), under uint16
-	// RGBA's conditions
+	// ... or the half / bfloat16 RGBA image, stored as the same type (io 6 /
+	// 7), under uint16 RGBA's conditions
 	int srck = 0;
 
 	if( raw != nullptr )
 	{
-		const bool half = ( p -> in_type == AVIRHIP_F16 );
+		// (1 half, 2 bfloat16: the io code of the same type is 5 + that)
+		const int f16kind = ( p -> in_type == AVIRHIP_F16 ? 1 :
+			( p -> in_type == AVIRHIP_BF16 ? 2 : 0 ));
 		const int esz = ( p -> in_type == AVIRHIP_U8 ? 1 : 2 );
 		const long sb = raw_stride * esz;
 
-		if(( half ? io != 6 || p -> io_ch != 4 : ( io != 4 && io != 5 ) ||
+		if(( f16kind ? io != 5 + f16kind || p -> io_ch != 4 :
+			( io != 4 && io != 5 ) ||
 			( p -> in_type != AVIRHIP_U8 && p -> in_type != AVIRHIP_U16 )) ||
 			( p -> io_ch != 3 && p -> io_ch != 4 ) ||
 			win.rows > 0 || ( (uintptr_t) raw & ( esz - 1 )) ||
@@ -1733,7 +1766,7 @@ int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 			return( 1 );
 		}
 
-		srck = ( half ? 100 : 0 ) + esz * 10 + p -> io_ch;
+		srck = f16kind * 100 + esz * 10 + p -> io_ch;
 		src = (const float*) raw;
 		src_stride = sb;
 	}
@@ -1768,7 +1801,7 @@ int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 	P.nstrips = ( p -> new_w + U2_TW - 1 ) / U2_TW;
 	P.ibase = iout; P.ich = p -> io_ch;
 	P.istride_b = p -> new_w * p -> io_ch * ( io == 1 || io == 4 ? 1 :
-		( io == 2 || io == 5 || io == 6 ? 2 : 4 ));
+		( io == 2 || io == 5 || io == 6 || io == 7 ? 2 : 4 ));
 
 	// Chunk heights (up2_chunks.h). A chunk of h source rows costs
 	// ( h + 18 ) / U2_RB marching steps (6 rows of preload + 12 of warm-up), so
@@ -1845,6 +1878,11 @@ int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 			U2_RAW( 6, 124 );
 		}
 		else
+		if( io == 7 )
+		{
+			U2_RAW( 7, 224 );
+		}
+		else
 		if( io == 4 )
 		{
 			switch( srck )
@@ -1881,6 +1919,8 @@ int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 			case 4: hipLaunchKernelGGL(( k_up2< U2_RB == 8, U2_RB == 8 ? 4 : 0 > ),
 				dim3( items ), dim3( U2_NT ), ldspad, st, P ); break;
 			case 6: hipLaunchKernelGGL(( k_up2< U2_RB == 8, U2_RB == 8 ? 6 : 0 > ),
+				dim3( items ), dim3( U2_NT ), ldspad, st, P ); break;
+			case 7: hipLaunchKernelGGL(( k_up2< U2_RB == 8, U2_RB == 8 ? 7 : 0 > ),
 				dim3( items ), dim3( U2_NT ), ldspad, st, P ); break;
 			default: hipLaunchKernelGGL(( k_up2< U2_RB == 8, U2_RB == 8 ? 5 : 0 > ),
 				dim3( items ), dim3( U2_NT ), ldspad, st, P ); break;

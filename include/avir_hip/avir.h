@@ -204,6 +204,10 @@ template<> struct dtype_of< double > { static const int v = AVIRHIP_F64; };
 // half images (the float32 call, widened / narrowed: avirhip.h AVIRHIP_F16)
 template<> struct dtype_of< _Float16 > { static const int v = AVIRHIP_F16; };
 #endif
+#ifdef AVIRHIP_HAS_BF16
+// bfloat16 images (the same rule: avirhip.h AVIRHIP_BF16)
+template<> struct dtype_of< __bf16 > { static const int v = AVIRHIP_BF16; };
+#endif
 
 /* Memory exhaustion comes back from the library as a code (no exception
  * crosses its C boundary) and leaves here as what the reference itself throws,

@@ -147,6 +147,9 @@ template<> struct CLancIR :: dt< double > { static const int v = AVIRHIP_F64; };
 #ifdef __FLT16_MANT_DIG__
 template<> struct CLancIR :: dt< _Float16 > { static const int v = AVIRHIP_F16; };
 #endif
+#ifdef AVIRHIP_HAS_BF16
+template<> struct CLancIR :: dt< __bf16 > { static const int v = AVIRHIP_BF16; };
+#endif
 /* "`uint32_t` type is treated as `uint16_t`" (lancir.h:376-377): 32-bit
  * elements, 0..65535 value range. */
 template<> struct CLancIR :: dt< uint32_t > { static const int v = AVIRHIP_U32; };

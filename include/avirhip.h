@@ -66,8 +66,38 @@ typedef enum avirhip_dtype {
 	 * mixes freely with the other types. fpclass_float4 and fpclass_def<double>
 	 * refuse half elements (AVIRHIP_EUNSUPPORTED): their float results pass
 	 * through an output stage of their own -- a different contract. */
-	AVIRHIP_F16 = 5
+	AVIRHIP_F16 = 5,
+	/* bfloat16 elements: 16 bits holding the upper half of an IEEE binary32.
+	 * A call with bfloat16 elements is DEFINED by the same call with float
+	 * buffers, as AVIRHIP_F16's is. Source: each element is widened exactly,
+	 * float bits = element bits << 16, for every bit pattern (denormals
+	 * included; a NaN stays a NaN), and the call then behaves in every respect
+	 * as a float32 source does (scaling, SrcBitDepth, gamma linearisation,
+	 * channel padding). Result: the call computes exactly the float32 result
+	 * fpclass_def<float> / CLancIR would store into a float32 destination (with
+	 * UseSRGBGamma it stays linear; no clamp, no PkOut scale, not dithered), and
+	 * each element u (float bits) is narrowed round-to-nearest-even:
+	 * ( u + 0x7fff + (( u >> 16 ) & 1 )) >> 16 for every non-NaN u -- float32
+	 * denormals become bfloat16 denormals, values that round beyond the largest
+	 * finite bfloat16 become +-Inf; a NaN becomes a NaN of unspecified payload
+	 * and sign. The two sides are independent: bfloat16 mixes freely with every
+	 * other type, AVIRHIP_F16 included. fpclass_float4 and fpclass_def<double>
+	 * refuse bfloat16 elements (AVIRHIP_EUNSUPPORTED) as they refuse half ones;
+	 * CLancIR accepts them on either side under the same rule. */
+	AVIRHIP_BF16 = 6
 } avirhip_dtype;
+
+/* Whether the compiler has the `__bf16` storage type (the C++ front ends map
+ * it to AVIRHIP_BF16). g++ (13 and later) announces it with
+ * __BFLT16_MANT_DIG__; clang predefines no macro for it, so there the test is
+ * the version that brought the type to the target: x86 with SSE2, AArch64,
+ * AMDGPU. (Of these, the tests build with the HIP toolchain's clang on x86
+ * alone.) */
+#if defined( __BFLT16_MANT_DIG__ ) || ( defined( __clang__ ) && \
+	__clang_major__ >= 15 && ( defined( __SSE2__ ) || defined( __aarch64__ ) || \
+	defined( __AMDGPU__ )))
+#define AVIRHIP_HAS_BF16 1
+#endif
 
 /* Where a buffer passed to an execute call lives. */
 #define AVIRHIP_MEM_HOST 0
@@ -288,7 +318,7 @@ int avirhip_plan_get_path(const avirhip_plan* plan);
 #define AVIRHIP_VARIANT_SACC_OPTIMISTIC 32
 /* path 4: the marching kernel reads the pack pass' float copy of the source and
  * writes a float result for the output stage, where it would read or store the
- * caller's integer / half pixels itself (the A/B and differential form of the
+ * caller's integer / half / bfloat16 pixels itself (the A/B and differential form of the
  * fused I/O; float RGBA images are the kernel's own format either way) */
 #define AVIRHIP_VARIANT_UP2_UNFUSED_IO 64
 int avirhip_plan_set_variant(avirhip_plan* plan, int variant);

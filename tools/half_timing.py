@@ -10,8 +10,12 @@ one process, avirhip_time_resize, every figure over a ring of distinct source /
 destination pairs of more than 512 MiB in all (twice the Infinity Cache), the
 rows alternating REPS times. Prints the table with the achieved bytes/s, the
 library's md5 and the device clocks.
+--bf16 adds the bfloat16 rows beside them, in the same process and rotation:
+  (e) bfloat16 -> bfloat16, read and stored by k_up2 (k_up2< true, 7, 224 >),
+  (f) bfloat16 -> bfloat16 through the pack pass and the output stage,
+  (g) float32 -> bfloat16 (k_up2< true, 7 >).
 
-usage: python tools/half_timing.py [PARENT.so] [REPS=5]"""
+usage: python tools/half_timing.py [--bf16] [PARENT.so] [REPS=5]"""
 import ctypes as C
 import hashlib
 import os
@@ -32,8 +36,10 @@ def main():
     import torch
     import avir_amd
     from avir_amd import abi, synth
-    parent = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1] != "-" else None
-    reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    argv = [a for a in sys.argv if a != "--bf16"]
+    bf16 = len(argv) != len(sys.argv)
+    parent = argv[1] if len(argv) > 1 and argv[1] != "-" else None
+    reps = int(argv[2]) if len(argv) > 2 else 5
     lib = abi.load()
     dev = torch.device("cuda", 0)
     st = torch.cuda.current_stream(dev).cuda_stream
@@ -50,8 +56,9 @@ def main():
                 print("clocks  " + l.strip())
     except Exception as e:  # (the table stands without them)
         print("clocks  unavailable: %r" % (e,))
-    TD = {abi.F32: torch.float32, abi.F16: torch.float16}
-    ES = {abi.F32: 4, abi.F16: 2}
+    TD = {abi.F32: torch.float32, abi.F16: torch.float16,
+          abi.BF16: torch.bfloat16}
+    ES = {abi.F32: 4, abi.F16: 2, abi.BF16: 2}
     for name, (sw, sh) in (("cfg3", (3840, 2160)), ("cfg2", (1920, 1080))):
         nw, nh = 2 * sw, 2 * sh
         base = synth.lcg_f32((sh, sw, 4))
@@ -60,6 +67,14 @@ def main():
                 ("c  f16->f16 pack + output stage", lib, abi.F16, abi.F16,
                  abi.VARIANT_UP2_UNFUSED_IO),
                 ("d  f32->f16", lib, abi.F32, abi.F16, 0)]
+        pairs = [("b  f16->f16 fused", "c  f16->f16 pack + output stage")]
+        if bf16:
+            rows += [("e  bf16->bf16 fused", lib, abi.BF16, abi.BF16, 0),
+                     ("f  bf16->bf16 pack + output stage", lib, abi.BF16,
+                      abi.BF16, abi.VARIANT_UP2_UNFUSED_IO),
+                     ("g  f32->bf16", lib, abi.F32, abi.BF16, 0)]
+            pairs.append(("e  bf16->bf16 fused",
+                          "f  bf16->bf16 pack + output stage"))
         if parent:
             rows.insert(0, ("a' f32->f32 parent build", abi.load_path(parent),
                             abi.F32, abi.F32, 0))
@@ -95,9 +110,8 @@ def main():
             for _ in range(20):
                 run[tag][0]()
         torch.cuda.synchronize()
-        same = torch.equal(first["b  f16->f16 fused"].view(torch.uint8),
-                           first["c  f16->f16 pack + output stage"].view(
-                               torch.uint8))
+        same = [torch.equal(first[x].view(torch.uint8),
+                            first[y].view(torch.uint8)) for x, y in pairs]
         res = {tag: [] for tag in run}
         loops = 30 if name == "cfg3" else 60
         for _ in range(reps):
@@ -112,7 +126,9 @@ def main():
                   "%.2f TB/s  ring %d" % (
                       tag, med, v[0], v[-1], run[tag][1] / 1e6,
                       run[tag][1] / med / 1e9, run[tag][2]), flush=True)
-        print("  (b) and (c) bit-identical: %s" % same, flush=True)
+        print("  (b) and (c) bit-identical: %s" % same[0], flush=True)
+        if bf16:
+            print("  (e) and (f) bit-identical: %s" % same[1], flush=True)
         del keep, run, first
         torch.cuda.empty_cache()
 
