@@ -422,11 +422,16 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 	// (raw sources: a dword-aligned base -- its two low bits go into the lanes'
 	// offsets -- and the range the image's bytes end in, rounded up to a dword:
 	// a pixel's second dword beyond it reads 0 without touching memory)
+	// (the image may end 2 GiB or more above this work item's base: the range
+	// is computed in long and stops at the largest one -- the rows this item
+	// reads, at most U2_RB * UP2_KMAX of a pitch below 1 << 22, end below it)
 	const char* const sbase = (const char*) P.src + (long) ubase * srow_b;
 	const int rsh = ( SRC != 0 ? (int) ( (unsigned long long) sbase & 3 ) : 0 );
+	const long rend = ( rsh + (long) ( P.rmax - ubase ) * srow_b +
+		(long) P.sw * PXB + 3 ) & ~3L;
 	const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
 		(void*) ( sbase - rsh ), 0, ( SRC != 0 ?
-		( rsh + ( P.rmax - ubase ) * srow_b + P.sw * PXB + 3 ) & ~3 : 0x7fffffff ),
+		(int) ( rend < 0x7ffffffcL ? rend : 0x7ffffffcL ) : 0x7fffffff ),
 		0x00020000 );
 	const __amdgpu_buffer_rsrc_t rdst = __builtin_amdgcn_make_buffer_rsrc(
 		(void*) ( P.dst + (long) ( qy0 * 2 - P.dst_row0 ) * P.dst_ss ), 0,
