@@ -931,12 +931,16 @@ static int lancir_owner( avirhip_plan* p, const void* src, void* dst,
 		( (uintptr_t) dst & ( p -> io_ch == 3 ? 1 : 3 )) == 0 ) &&
 		( p -> out_type != AVIRHIP_F32 || ( (uintptr_t) dst & 3 ) == 0 ));
 
+	// (AVIRHIP_VARIANT_UP2_UNFUSED_IO: the process-wide switch, per plan)
+	const bool fio = ( fused_io() &&
+		!( p -> variant & AVIRHIP_VARIANT_UP2_UNFUSED_IO ));
+
 	// the inner plan's first pass reads this image itself where it can;
 	// otherwise the pack pass makes its float RGBA copy
-	const ImageRef* raw = ( fused_io() && in_fast &&
+	const ImageRef* raw = ( fio && in_fast &&
 		( gpass_lancir_takes_raw( q, img ) ||
 		( lanc2_takes_raw( q, img ) && dst2 )) ? &img : nullptr );
-	const LancirOut* const lout = ( fused_io() && out_fast ? &ostage : nullptr );
+	const LancirOut* const lout = ( fio && out_fast ? &ostage : nullptr );
 
 	auto pack = [&]() -> int
 	{
@@ -960,6 +964,55 @@ static int lancir_owner( avirhip_plan* p, const void* src, void* dst,
 		return( need_floats( p, &p -> lres,
 			(size_t) p -> new_w * p -> new_h * 4 ));
 	};
+
+	// Exact 2x RGBA with a half / bfloat16 image on either side (lanc2h.hip):
+	// one launch, on the automatic path whatever the frame's size (the pass
+	// kernels know neither type: behind them the pack pass and the output
+	// stage would run) and on forced path 4. A half / bfloat16 RESULT is
+	// narrowed and stored by the kernel, whatever the source: the kernel reads
+	// a half / bfloat16 / float RGBA source where it lies, the pack pass's
+	// float copy of any other. A half / bfloat16 SOURCE with a float result is
+	// the kernel's too (the caller's image when the plan is unity, `lres` and
+	// the output stage otherwise); with an integer result it is not: that is
+	// k_lanc2's fused store behind the pack pass, below. An image that
+	// lanc2h_image_ok refuses goes through its float copy, and a call left
+	// with float on both sides takes the general road below.
+	const bool h_in = dtype_is_float16_kind( p -> in_type );
+	const bool h_out = dtype_is_float16_kind( p -> out_type );
+
+	if( fio && ( h_out || ( h_in && p -> out_type == AVIRHIP_F32 )) &&
+		p -> io_ch == 4 && q -> l_order == 4 && q -> lanc2 != nullptr &&
+		( p -> path == 0 || p -> path == 4 ))
+	{
+		const bool src_own = (( h_in || p -> in_type == AVIRHIP_F32 ) &&
+			lanc2h_image_ok( src, p -> in_type, p -> src_stride ));
+		const bool dst_own = (( h_out || p -> l_unity ) &&
+			lanc2h_image_ok( dst, p -> out_type, p -> new_stride ));
+
+		if(( src_own && h_in ) || ( dst_own && h_out ))
+		{
+			if( !src_own && ( rc = pack()) != 0 ) return( rc );
+			if( !dst_own && ( rc = need_lres()) != 0 ) return( rc );
+
+			const ImageRef hsrc = ( src_own ? img : ImageRef{ p -> packed,
+				AVIRHIP_F32, 4, (long) p -> src_w * 4 });
+			const LancirOut hout = ( dst_own ? ostage : LancirOut{ p -> lres,
+				(long) p -> new_w * 4, AVIRHIP_F32, 4, 1, 1.0f, 0.0f });
+
+			rc = lanc2h_run( q, hsrc, hout, row0, row1, st );
+
+			if( rc == 0 && !dst_own )
+			{
+				rc = launch_lancir_out( p, p -> lres, (long) p -> new_w * 4, dst,
+					row1 - row0, st );
+			}
+
+			if( rc != 1 )
+			{
+				return( rc );
+			}
+		}
+	}
 
 	if( raw == nullptr && ( rc = pack()) != 0 ) return( rc );
 

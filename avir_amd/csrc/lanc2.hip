@@ -699,4 +699,13 @@ int lanc2_run( const avirhip_plan* p, const float* src, float* dst, int row0,
 	return( AVIRHIP_OK );
 }
 
+// The coefficient table of a plan lanc2_prepare matched (device, 32 floats:
+// Lanc2Params::coef), nullptr otherwise -- what lanc2h.hip's kernel shares
+// with this one.
+const float* lanc2_coef( const avirhip_plan* p )
+{
+	const Lanc2Data* D = (const Lanc2Data*) p -> lanc2;
+	return( D != nullptr ? D -> d_coef : nullptr );
+}
+
 } // namespace avirhip

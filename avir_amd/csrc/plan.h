@@ -480,5 +480,15 @@ int lanc2_run( const avirhip_plan* p, const float* src, float* dst, int row0,
 	int row1, hipStream_t st, SrcWindow win, const ImageRef* raw,
 	const LancirOut* lout );
 bool lanc2_takes_raw( const avirhip_plan* q, const ImageRef& raw );
+const float* lanc2_coef( const avirhip_plan* p );
+
+// lanc2h.hip: LANCIR exact-2x RGBA with half / bfloat16 images on either side,
+// one launch over the images where they lie (`q`: the inner float RGBA plan).
+// lanc2h_image_ok: what the kernel asks of an image (a pixel naturally
+// aligned; `stride` in elements); lanc2h_run returns 1 for a call that is not
+// its own (float on both sides, an image the predicate refuses).
+bool lanc2h_image_ok( const void* ptr, int type, long stride );
+int lanc2h_run( const avirhip_plan* q, const ImageRef& src,
+	const LancirOut& out, int row0, int row1, hipStream_t st );
 
 } // namespace avirhip

@@ -65,7 +65,11 @@ typedef enum avirhip_dtype {
 	 * +-65504 become +-Inf, NaN stays NaN. The two sides are independent: half
 	 * mixes freely with the other types. fpclass_float4 and fpclass_def<double>
 	 * refuse half elements (AVIRHIP_EUNSUPPORTED): their float results pass
-	 * through an output stage of their own -- a different contract. */
+	 * through an output stage of their own -- a different contract.
+ * (Two kernels read and store half RGBA pixels themselves, one launch over
+ * the caller's images: CImageResizer's exact-2x marching kernel k_up2 and
+ * CLancIR's exact-2x kernel k_lanc2h; everywhere else the pack pass widens
+ * and the output stage narrows.) */
 	AVIRHIP_F16 = 5,
 	/* bfloat16 elements: 16 bits holding the upper half of an IEEE binary32.
 	 * A call with bfloat16 elements is DEFINED by the same call with float
@@ -83,7 +87,9 @@ typedef enum avirhip_dtype {
 	 * and sign. The two sides are independent: bfloat16 mixes freely with every
 	 * other type, AVIRHIP_F16 included. fpclass_float4 and fpclass_def<double>
 	 * refuse bfloat16 elements (AVIRHIP_EUNSUPPORTED) as they refuse half ones;
-	 * CLancIR accepts them on either side under the same rule. */
+	 * CLancIR accepts them on either side under the same rule. (k_up2 and
+ * k_lanc2h read and store bfloat16 RGBA pixels themselves, as they do half
+ * ones.) */
 	AVIRHIP_BF16 = 6
 } avirhip_dtype;
 
@@ -319,7 +325,10 @@ int avirhip_plan_get_path(const avirhip_plan* plan);
 /* path 4: the marching kernel reads the pack pass' float copy of the source and
  * writes a float result for the output stage, where it would read or store the
  * caller's integer / half / bfloat16 pixels itself (the A/B and differential form of the
- * fused I/O; float RGBA images are the kernel's own format either way) */
+ * fused I/O; float RGBA images are the kernel's own format either way).
+ * On a CLancIR plan: the pack pass and the output stage always run, whatever
+ * the path -- no kernel reads the caller's image as it lies and none stores the
+ * caller's pixels itself (AVIRHIP_NO_FUSED_OUT for this plan alone) */
 #define AVIRHIP_VARIANT_UP2_UNFUSED_IO 64
 int avirhip_plan_set_variant(avirhip_plan* plan, int variant);
 

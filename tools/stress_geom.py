@@ -24,7 +24,8 @@ pass kernels around their ring depths (AVIRHIP_*_CHUNK, *_CQ: read per call).
 usage: python tools/stress_geom.py [cases=120] [seed=1] [repeats=4]
            [--against LIB.so] [--lib LIB.so] [--family F] [--chunks]
   --lib      the library under test (default: the product build / AVIRHIP_LIB)
-  --family   all | up2 | lanc2 | dnf | gpass_up | gf | lf | lanc_dn | sacc
+  --family   all | up2 | lanc2 | lanc2h | dnf | gpass_up | gf | lf | lanc_dn |
+             sacc
              (geometries that route to one kernel family; the summary counts the
              execution paths that actually ran)
   --chunks   force a random chunk length per case: below, at and above the ring
@@ -43,8 +44,17 @@ import numpy as np  # noqa: E402
 CHUNK_ENVS = ("AVIRHIP_GV_CHUNK", "AVIRHIP_GH_CHUNK", "AVIRHIP_GF_CHUNK",
               "AVIRHIP_LF_CHUNK", "AVIRHIP_SA_CHUNK", "AVIRHIP_UP2_CQ",
               "AVIRHIP_LANC2_CQ")
-FAMILIES = ("all", "up2", "lanc2", "dnf", "gpass_up", "gf", "lf", "lanc_dn",
-            "sacc")
+FAMILIES = ("all", "up2", "lanc2", "lanc2h", "dnf", "gpass_up", "gf", "lf",
+            "lanc_dn", "sacc")
+BF16 = "bfloat16"  # (numpy has no such type: the name stands for it)
+# k_lanc2h's (SRC, OUT) pairs: every one but float -> float
+LANC2H_PAIRS = [(a, b) for a in (np.float16, BF16, np.float32)
+                for b in (np.float16, BF16, np.float32)
+                if not (a is np.float32 and b is np.float32)]
+
+
+def tname(t):
+    return t if isinstance(t, str) else np.dtype(t).name
 
 
 def gen_case(rng, family, big):
@@ -82,6 +92,16 @@ def gen_case(rng, family, big):
         ch = 4 if rng.rand() < 0.7 else int(rng.choice([1, 3]))
         if rng.rand() < 0.6:
             tin = tout = np.float32
+    elif family == "lanc2h":
+        # CLancIR exact 2x RGBA with half / bfloat16 images on either side:
+        # k_lanc2h at every frame size (strips of 128 output columns, chunks
+        # of 58 source rows and more)
+        lanc = True
+        sw = int(rng.randint(100, 4000 if big else 2400))
+        sh = int(rng.randint(60, 2300 if big else 1400))
+        nw, nh = 2 * sw, 2 * sh
+        ch = 4
+        tin, tout = LANC2H_PAIRS[rng.randint(0, len(LANC2H_PAIRS))]
     elif family == "dnf":
         lanc = False
         d, e = int(rng.choice([2, 3])), int(rng.choice([2, 3]))
@@ -170,14 +190,15 @@ def main():
         th = threading.Thread(target=hammer, daemon=True)
         th.start()
 
+    def code(t):
+        return abi.BF16 if t == BF16 else avir_amd._NP2T[np.dtype(t)]
+
     def make(L, lanc, sw, sh, nw, nh, ch, tin, tout):
         """front-end object + plan of library L"""
         with abi.using(L):
             if lanc:
                 r = avir_amd.CLancIR()
-                p = r.plan(sw, sh, nw, nh, ch, None,
-                           avir_amd._NP2T[np.dtype(tin)],
-                           avir_amd._NP2T[np.dtype(tout)])
+                p = r.plan(sw, sh, nw, nh, ch, None, code(tin), code(tout))
             else:
                 r = avir_amd.CImageResizer(8 if tout == np.uint8 else 16)
                 p = r.plan(sw, sh, nw, nh, ch, 0.0, None,
@@ -216,16 +237,18 @@ def main():
             os.environ["AVIRHIP_UP2_CQ"] = str(cq)
             os.environ["AVIRHIP_LANC2_CQ"] = str(cq)
             chunk_note = " chunk %d cq %d" % (c, cq)
-        if np.dtype(tin).kind == "u":
+        if tin != BF16 and np.dtype(tin).kind == "u":
             s = synth.lcg_u8((sh, sw, ch, np.dtype(tin).itemsize),
                              seed=it + 11).view(tin).reshape(sh, sw, ch)
         else:
             s = synth.lcg_f32((sh, sw, ch), seed=it + 11)
-        ds = torch.from_numpy(s).to(dev)
-        tt = {np.uint8: torch.uint8, np.uint16: torch.uint16,
-              np.float32: torch.float32}[tout]
+        TT = {np.uint8: torch.uint8, np.uint16: torch.uint16,
+              np.float32: torch.float32, np.float16: torch.float16,
+              BF16: torch.bfloat16}
+        ds = torch.from_numpy(s).to(dev).to(TT[tin])
+        tt = TT[tout]
         what = ("lancir" if lanc else "avir", sw, sh, nw, nh, ch,
-                np.dtype(tin).name, np.dtype(tout).name)
+                tname(tin), tname(tout))
         shape = (nh, nw, ch)
         want = None
         # ---- the result that cannot carry the race
@@ -274,7 +297,7 @@ def main():
             abi.check(lib.avirhip_plan_set_variant(p, 0), "v")
             if ref is not None:
                 abi.check(ref.avirhip_plan_set_variant(rp, 0), "v")
-        if os.environ.get("STRESS_HOST") is not None:
+        if os.environ.get("STRESS_HOST") is not None and BF16 not in (tin, tout):
             # ... and as the drop-in call makes it: host pointers (frames
             # of 16 MiB and more run the 16-band copy / compute pipeline)
             for k in range(2):
