@@ -32,6 +32,7 @@ VARIANT_UP2_PLAIN_V, VARIANT_DN_TWO_PASS, VARIANT_SACC_LADDER = 1, 2, 4
 VARIANT_UPG_TWO_PASS, VARIANT_UPG_FUSED = 8, 16
 VARIANT_SACC_OPTIMISTIC = 32
 VARIANT_UP2_UNFUSED_IO = 64
+VARIANT_DN_UNFUSED_IO = 128
 FPCLASS_DOUBLE = 64  # avirhip_resizer_set_fpclass: fpclass_def<double>
 
 _fp = C.POINTER(C.c_float)

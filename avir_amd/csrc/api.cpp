@@ -596,6 +596,10 @@ void need_range( const LOp& op, int a, int b, int& ia, int& ib )
 	ib = std::max( 0, std::min( ib, op.in_len - 1 ));
 }
 
+// The float copies a call may need, allocated up front: every road but
+// k_dnfh's (avir_dn16) calls this first. That road skips it, and avir_pack
+// (`packed`) and avir_need_res (`resbuf`) allocate each when something is about
+// to use it -- the same sizes as here, so after this function they are no-ops.
 static int ensure_scratch( avirhip_plan* p )
 {
 	int rc;
@@ -1092,6 +1096,14 @@ static int avir_pack( avirhip_plan* p, AvirSrc& S, int row0, int row1,
 
 	S.packed = true;
 
+	// (the road of avir_dn16 comes here without ensure_scratch -- its refused
+	// calls and exec_avir's generic fall-back behind it; a no-op elsewhere)
+	const int ra = need_floats( p, &p -> packed, (size_t) p -> src_w *
+		p -> src_h * p -> ch );
+
+	if( ra != 0 ) return( ra );
+	S.f = p -> packed;
+
 	// a band converts the source rows its windows read, nothing else (the
 	// pipelined host-pointer call is 16 bands: 16 whole-frame packs otherwise)
 	int pa, pb;
@@ -1117,13 +1129,43 @@ static int avir_pack( avirhip_plan* p, AvirSrc& S, int row0, int row1,
 		p -> io_ch, p -> ch, p -> src_stride, st ));
 }
 
+// Whole-ratio downsizing on both axes (path 2) with half / bfloat16 pixels on a
+// side, no gamma, the default ditherer: k_dnfh's road (avir_fast) -- one launch
+// that reads a 16-bit RGBA source where it lies and narrows and stores a 16-bit
+// result itself. Such a call allocates `packed` and `resbuf` only when
+// something is about to use them. AVIRHIP_VARIANT_DN_UNFUSED_IO: today's road
+// (pack pass, k_dnf, output stage).
+static bool avir_dn16( const avirhip_plan* p, const int path )
+{
+	return( path == 2 && !p -> gamma && p -> ch == 4 &&
+		p -> dither == AVIRHIP_DITHER_DEF && fused_io() &&
+		( dtype_is_float16_kind( p -> in_type ) ||
+		dtype_is_float16_kind( p -> out_type )) &&
+		!( p -> variant & AVIRHIP_VARIANT_DN_UNFUSED_IO ) && fused_dn16( p ));
+}
+
+// the float result buffer of a call that is not `direct`, when it is needed
+static int avir_need_res( avirhip_plan* p, float*& fdst, const bool direct )
+{
+	if( direct )
+	{
+		return( AVIRHIP_OK );
+	}
+
+	const int rc = need_floats( p, &p -> resbuf, (size_t) p -> new_w *
+		p -> new_h * p -> ch );
+
+	fdst = p -> resbuf;
+	return( rc );
+}
+
 // The fast paths of an AVIR call: 5 (pass kernels), 4 (exact-2x marching
 // kernel), 2 / 3 (LDS tiles). Returns 1 when the path cannot take the call
 // (the generic chain does), 0 when it ran: `stored` -- its last pass converted
 // and stored the caller's pixels at `dst`; otherwise the float result is at
 // `fdst`. `direct`: the caller's image IS the float result (fdst == dst).
 static int avir_fast( avirhip_plan* p, const int path, AvirSrc& S, void* dst,
-	float* fdst, const bool direct, int row0, int row1, hipStream_t st,
+	float*& fdst, const bool direct, int row0, int row1, hipStream_t st,
 	const SrcWindow win, bool& stored )
 {
 	int rc;
@@ -1163,9 +1205,51 @@ static int avir_fast( avirhip_plan* p, const int path, AvirSrc& S, void* dst,
 		p -> dither == AVIRHIP_DITHER_DEF && up2_stores_io( p ) && fio :
 		int_in && fused_takes_raw( p, path )));
 
-	if( !raw && ( rc = avir_pack( p, S, row0, row1, st )) != 0 ) return( rc );
-
 	stored = false;
+
+	if( avir_dn16( p, path ))
+	{
+		// the source k_dnfh reads: the caller's half / bfloat16 / float RGBA
+		// image where it lies, the pack pass's float copy of any other (and
+		// of one lanc2h_image_ok refuses: a misaligned base, an odd pitch)
+		const bool h_out = dtype_is_float16_kind( p -> out_type );
+		const bool src_own = ( p -> io_ch == 4 &&
+			( dtype_is_float16_kind( p -> in_type ) || !S.need_pack ) &&
+			lanc2h_image_ok( S.img, p -> in_type, p -> src_stride ));
+		// the result: narrowed and stored by the kernel (half / bfloat16),
+		// through the integer output stage as k_dnf's, or float rows
+		void* const hout = ( direct ? nullptr : h_out ?
+			(( (uintptr_t) dst & 1 ) == 0 ? dst : nullptr ) :
+			( stores && !( p -> out_type == AVIRHIP_U8 && p -> io_ch == 4 &&
+			( (uintptr_t) dst & 3 ) != 0 ) && fused_stores_int( p, path ) ?
+			dst : nullptr ));
+
+		if(( src_own && p -> in_type != AVIRHIP_F32 ) ||
+			( hout != nullptr && h_out ))
+		{
+			if( !src_own && ( rc = avir_pack( p, S, row0, row1, st )) != 0 )
+				return( rc );
+
+			if( hout == nullptr &&
+				( rc = avir_need_res( p, fdst, direct )) != 0 ) return( rc );
+
+			const ImageRef hsrc = ( src_own ? img : ImageRef{ S.f,
+				AVIRHIP_F32, 4, S.fstride });
+
+			rc = fused_run_dn16( p, hsrc, fdst, row0, row1, st, hout );
+
+			if( rc != 1 )
+			{
+				stored = ( rc == 0 && hout != nullptr );
+				return( rc );
+			}
+		}
+
+		// (today's road: the float result, where the call has one)
+		if(( rc = avir_need_res( p, fdst, direct )) != 0 ) return( rc );
+	}
+
+	if( !raw && ( rc = avir_pack( p, S, row0, row1, st )) != 0 ) return( rc );
 
 	if( path == 5 )
 	{
@@ -1274,10 +1358,12 @@ static int avir_output( avirhip_plan* p, const float* fdst, void* dst,
 static int exec_avir( avirhip_plan* p, const void* src, void* dst, int row0,
 	int row1, hipStream_t st, const SrcWindow win )
 {
-	int rc = ensure_scratch( p );
+	const int path = ( p -> path != 0 ? p -> path : p -> auto_path );
+	// (k_dnfh's road makes neither float copy: avir_pack and avir_need_res
+	// allocate them where a refused call needs them after all)
+	int rc = ( avir_dn16( p, path ) ? AVIRHIP_OK : ensure_scratch( p ));
 	if( rc != 0 ) return( rc );
 
-	const int path = ( p -> path != 0 ? p -> path : p -> auto_path );
 	const bool need_pack = ( p -> gamma || p -> in_type != AVIRHIP_F32 ||
 		p -> ch != p -> io_ch );
 	AvirSrc S = { src, ( need_pack ? p -> packed : (const float*) src ),
@@ -1291,7 +1377,7 @@ static int exec_avir( avirhip_plan* p, const void* src, void* dst, int row0,
 	// the output stage like every other type, which matters with gamma)
 	const bool direct = ( p -> out_type == AVIRHIP_F32 &&
 		p -> ch == p -> io_ch && !( p -> fp4 && p -> gamma ));
-	float* const fdst = ( direct ? (float*) dst : p -> resbuf );
+	float* fdst = ( direct ? (float*) dst : p -> resbuf );
 
 	rc = 1;
 
@@ -1317,6 +1403,7 @@ static int exec_avir( avirhip_plan* p, const void* src, void* dst, int row0,
 	if( rc == 1 )
 	{
 		if(( rc = avir_pack( p, S, row0, row1, st )) != 0 ) return( rc );
+		if(( rc = avir_need_res( p, fdst, direct )) != 0 ) return( rc );
 		rc = run_generic( p, S.f, S.fstride, fdst, row0, row1, st );
 	}
 
@@ -3056,7 +3143,7 @@ int avirhip_plan_set_variant( avirhip_plan* p, int variant )
 try
 {
 	avirhip::clear_error();
-	if( p == nullptr || variant < 0 || variant > 127 )
+	if( p == nullptr || variant < 0 || variant > 255 )
 	{
 		set_error( "bad variant" );
 		return( AVIRHIP_EINVAL );

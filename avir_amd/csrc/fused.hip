@@ -1144,4 +1144,39 @@ int fused_run( avirhip_plan* p, int mode, const void* src, int src_type,
 		AVIRHIP_F32, 4, dss, dst, dss, row0, row0, row1, st ));
 }
 
+// Mode 2 of this plan is the one-launch kernel: both axes are whole-ratio
+// downsizing and neither AVIRHIP_DNF=0 nor the two-pass variant asks for the
+// pass kernels.
+bool fused_dn16( const avirhip_plan* p )
+{
+	const FusedData* F = (const FusedData*) p -> fused;
+	return( F != nullptr && ( p -> fused_ok & 1 ) && dn_has_h( F -> dn ) &&
+		dn_has_v( F -> dn ) && dnf_enabled() &&
+		!( p -> variant & AVIRHIP_VARIANT_DN_TWO_PASS ));
+}
+
+// Mode 2 with a half / bfloat16 image on a side (k_dnfh, dnf.hip): the source
+// read where it lies, the caller's pixels stored by the kernel (`iout`), or
+// float RGBA rows to `dst`. 1: the call takes fused_run's road.
+int fused_run_dn16( avirhip_plan* p, const ImageRef& src, float* dst, int row0,
+	int row1, hipStream_t st, void* iout )
+{
+	const FusedData* F = (const FusedData*) p -> fused;
+
+	if( !fused_dn16( p ))
+	{
+		return( 1 );
+	}
+
+	GPOut O;
+
+	if( iout != nullptr )
+	{
+		gp_make_out( p, iout, O );
+	}
+
+	return( dn_run_hv16( F -> dn, src, dst, row0, row1, st,
+		( iout != nullptr ? &O : nullptr )));
+}
+
 } // namespace avirhip

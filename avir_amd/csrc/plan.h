@@ -445,6 +445,19 @@ int dn_run_v( void* d, const float* flt, long flt_ss, int width, float* dst,
 // returns 1 when the call cannot take it
 int dn_run_hv( void* d, const float* src, long src_ss, float* dst, int row0,
 	int row1, hipStream_t st, const GPOut* out = nullptr );
+// ... with half / bfloat16 pixels on a side (k_dnfh): RGBA rows of `src` read
+// where they lie (half, bfloat16, float), float RGBA rows to `dst` or the
+// caller's pixels through `out` (half / bfloat16 narrowed in the store). 1: the
+// call is not its own (float on both sides, an image lanc2h_image_ok refuses,
+// rows beyond a 32-bit byte offset)
+int dn_run_hv16( void* d, const ImageRef& src, float* dst, int row0, int row1,
+	hipStream_t st, const GPOut* out );
+// fused.hip: whether mode 2 of this plan is the one-launch kernel (both axes
+// whole-ratio downsizing, not switched off), and its call with a half /
+// bfloat16 image on a side; `iout`: the caller's rows the kernel stores itself
+bool fused_dn16( const avirhip_plan* p );
+int fused_run_dn16( avirhip_plan* p, const ImageRef& src, float* dst, int row0,
+	int row1, hipStream_t st, void* iout );
 
 // gpass.hip: general-ratio pass kernels (path 5), AVIR and LANCIR RGBA float
 int gpass_prepare( avirhip_plan* p );

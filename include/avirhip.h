@@ -66,10 +66,11 @@ typedef enum avirhip_dtype {
 	 * mixes freely with the other types. fpclass_float4 and fpclass_def<double>
 	 * refuse half elements (AVIRHIP_EUNSUPPORTED): their float results pass
 	 * through an output stage of their own -- a different contract.
- * (Two kernels read and store half RGBA pixels themselves, one launch over
- * the caller's images: CImageResizer's exact-2x marching kernel k_up2 and
- * CLancIR's exact-2x kernel k_lanc2h; everywhere else the pack pass widens
- * and the output stage narrows.) */
+ * (Three kernels read and store half RGBA pixels themselves, one launch over
+ * the caller's images: CImageResizer's exact-2x marching kernel k_up2, its
+ * whole-ratio (2x, 3x) downsizing kernel k_dnfh, and CLancIR's exact-2x kernel
+ * k_lanc2h; everywhere else the pack pass widens and the output stage
+ * narrows.) */
 	AVIRHIP_F16 = 5,
 	/* bfloat16 elements: 16 bits holding the upper half of an IEEE binary32.
 	 * A call with bfloat16 elements is DEFINED by the same call with float
@@ -87,9 +88,9 @@ typedef enum avirhip_dtype {
 	 * and sign. The two sides are independent: bfloat16 mixes freely with every
 	 * other type, AVIRHIP_F16 included. fpclass_float4 and fpclass_def<double>
 	 * refuse bfloat16 elements (AVIRHIP_EUNSUPPORTED) as they refuse half ones;
-	 * CLancIR accepts them on either side under the same rule. (k_up2 and
- * k_lanc2h read and store bfloat16 RGBA pixels themselves, as they do half
- * ones.) */
+	 * CLancIR accepts them on either side under the same rule. (k_up2, k_dnfh
+ * and k_lanc2h read and store bfloat16 RGBA pixels themselves, as they do
+ * half ones.) */
 	AVIRHIP_BF16 = 6
 } avirhip_dtype;
 
@@ -330,6 +331,11 @@ int avirhip_plan_get_path(const avirhip_plan* plan);
  * the path -- no kernel reads the caller's image as it lies and none stores the
  * caller's pixels itself (AVIRHIP_NO_FUSED_OUT for this plan alone) */
 #define AVIRHIP_VARIANT_UP2_UNFUSED_IO 64
+/* path 2, whole-ratio downsizing on both axes with half / bfloat16 pixels on a
+ * side: the pack pass, k_dnf and the output stage run (two float copies on the
+ * plan) where k_dnfh would read and store the caller's 16-bit pixels in its
+ * one launch (the A/B and differential form of that kernel) */
+#define AVIRHIP_VARIANT_DN_UNFUSED_IO 128
 int avirhip_plan_set_variant(avirhip_plan* plan, int variant);
 
 /* Device memory the plan holds right now, in bytes: tables, scratch buffers

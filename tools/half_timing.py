@@ -22,8 +22,17 @@ library's md5 and the device clocks.
       (AVIRHIP_VARIANT_UP2_UNFUSED_IO: the road before k_lanc2h),
   (d) float32 -> half, (e) half -> float32,
   (f) - (i) the bfloat16 twins of (b) - (e).
+--dnf measures whole-ratio downsizing on path 2 by the same method: cfg4
+(3840x2160 -> 1280x720 RGBA) and 3840x2160 -> 1920x1080 as
+  (a) float32 -> float32 (k_dnf; with PARENT.so also on that build),
+  (b) half -> half, one launch of k_dnfh< F16, F16 >,
+  (c) half -> half through the pack pass, k_dnf and the output stage
+      (AVIRHIP_VARIANT_DN_UNFUSED_IO: the road before k_dnfh),
+  (d) bfloat16 -> bfloat16 fused, (e) the same unfused,
+  (f) float32 -> half, (g) half -> float32.
 
-usage: python tools/half_timing.py [--bf16 | --lancir] [PARENT.so] [REPS=5]"""
+usage: python tools/half_timing.py [--bf16 | --lancir | --dnf] [PARENT.so]
+       [REPS=5]"""
 import ctypes as C
 import hashlib
 import os
@@ -146,9 +155,99 @@ def lancir_main(argv):
         torch.cuda.empty_cache()
 
 
+def dnf_main(argv):
+    """--dnf: the rows of the module docstring, CImageResizer plans on path 2."""
+    import numpy as np
+    import torch
+    import avir_amd
+    from avir_amd import abi, synth
+    parent = argv[1] if len(argv) > 1 and argv[1] != "-" else None
+    reps = int(argv[2]) if len(argv) > 2 else 5
+    lib = abi.load()
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    header(lib, parent)
+    TD = {abi.F32: torch.float32, abi.F16: torch.float16,
+          abi.BF16: torch.bfloat16}
+    ES = {abi.F32: 4, abi.F16: 2, abi.BF16: 2}
+    U = abi.VARIANT_DN_UNFUSED_IO
+    sw, sh = 3840, 2160
+    base = synth.lcg_f32((sh, sw, 4))
+    for name, (nw, nh) in (("cfg4", (1280, 720)), ("1080p", (1920, 1080))):
+        rows = [("a  f32->f32 k_dnf", lib, abi.F32, abi.F32, 0),
+                ("b  f16->f16 fused", lib, abi.F16, abi.F16, 0),
+                ("c  f16->f16 pack + k_dnf + output stage", lib, abi.F16,
+                 abi.F16, U),
+                ("d  bf16->bf16 fused", lib, abi.BF16, abi.BF16, 0),
+                ("e  bf16->bf16 pack + k_dnf + output stage", lib, abi.BF16,
+                 abi.BF16, U),
+                ("f  f32->f16", lib, abi.F32, abi.F16, 0),
+                ("g  f16->f32", lib, abi.F16, abi.F32, 0)]
+        pairs = [(rows[1][0], rows[2][0]), (rows[3][0], rows[4][0])]
+        if parent:
+            rows.insert(0, ("a' f32->f32 parent build", abi.load_path(parent),
+                            abi.F32, abi.F32, 0))
+        run, keep, first = {}, [], {}
+        for tag, L, ti, to, variant in rows:
+            pair = sw * sh * 4 * ES[ti] + nw * nh * 4 * ES[to]
+            n = max(2, -(-(512 << 20) // pair))
+            ring = []
+            for i in range(n):
+                s = torch.from_numpy(np.roll(base, i, axis=0)).to(dev).to(TD[ti])
+                d = torch.empty((nh, nw, 4), dtype=TD[to], device=dev)
+                ring.append((s, d))
+            with abi.using(L):
+                r = avir_amd.CImageResizer(16)
+                p = r.plan(sw, sh, nw, nh, 4, 0.0, None, ti, to)
+            abi.check(L.avirhip_plan_set_path(p, 2), "path 2")
+            if variant:
+                abi.check(L.avirhip_plan_set_variant(p, variant), "variant")
+            keep.append((r, ring))
+
+            def once(L=L, p=p, ring=ring):
+                t = 0.0
+                ms = C.c_double()
+                for s, d in ring:
+                    abi.check(L.avirhip_time_resize(
+                        p, s.data_ptr(), d.data_ptr(), 1, st, C.byref(ms)),
+                        "time_resize")
+                    t += ms.value
+                return t / len(ring)
+            run[tag] = (once, pair, n, L, p)
+            first[tag] = ring[0][1]
+        for tag in run:  # warm-up, clocks
+            for _ in range(20):
+                run[tag][0]()
+        torch.cuda.synchronize()
+        same = [torch.equal(first[x].view(torch.uint8),
+                            first[y].view(torch.uint8)) for x, y in pairs]
+        res = {tag: [] for tag in run}
+        loops = 40
+        for _ in range(reps):
+            for tag in run:
+                res[tag].append(sum(run[tag][0]() for _ in range(loops)) / loops)
+        print("%s (%dx%d -> %dx%d RGBA, path 2), %d reps x %d ring passes:" % (
+            name, sw, sh, nw, nh, reps, loops))
+        for tag in run:
+            v = sorted(res[tag])
+            med = v[len(v) // 2]
+            print("  %-42s %.4f ms  (min %.4f max %.4f)  %6.1f MB/call  "
+                  "%.2f TB/s  ring %d  plan holds %.1f MB" % (
+                      tag, med, v[0], v[-1], run[tag][1] / 1e6,
+                      run[tag][1] / med / 1e9, run[tag][2],
+                      run[tag][3].avirhip_plan_device_bytes(run[tag][4]) / 1e6),
+                  flush=True)
+        print("  (b) and (c) bit-identical: %s" % same[0], flush=True)
+        print("  (d) and (e) bit-identical: %s" % same[1], flush=True)
+        del keep, run, first
+        torch.cuda.empty_cache()
+
+
 def main():
     if "--lancir" in sys.argv:
         return lancir_main([a for a in sys.argv if a != "--lancir"])
+    if "--dnf" in sys.argv:
+        return dnf_main([a for a in sys.argv if a != "--dnf"])
     import numpy as np
     import torch
     import avir_amd

@@ -24,8 +24,8 @@ pass kernels around their ring depths (AVIRHIP_*_CHUNK, *_CQ: read per call).
 usage: python tools/stress_geom.py [cases=120] [seed=1] [repeats=4]
            [--against LIB.so] [--lib LIB.so] [--family F] [--chunks]
   --lib      the library under test (default: the product build / AVIRHIP_LIB)
-  --family   all | up2 | lanc2 | lanc2h | dnf | gpass_up | gf | lf | lanc_dn |
-             sacc
+  --family   all | up2 | lanc2 | lanc2h | dnf | dnfh | gpass_up | gf | lf |
+             lanc_dn | sacc
              (geometries that route to one kernel family; the summary counts the
              execution paths that actually ran)
   --chunks   force a random chunk length per case: below, at and above the ring
@@ -44,8 +44,8 @@ import numpy as np  # noqa: E402
 CHUNK_ENVS = ("AVIRHIP_GV_CHUNK", "AVIRHIP_GH_CHUNK", "AVIRHIP_GF_CHUNK",
               "AVIRHIP_LF_CHUNK", "AVIRHIP_SA_CHUNK", "AVIRHIP_UP2_CQ",
               "AVIRHIP_LANC2_CQ")
-FAMILIES = ("all", "up2", "lanc2", "lanc2h", "dnf", "gpass_up", "gf", "lf",
-            "lanc_dn", "sacc")
+FAMILIES = ("all", "up2", "lanc2", "lanc2h", "dnf", "dnfh", "gpass_up", "gf",
+            "lf", "lanc_dn", "sacc")
 BF16 = "bfloat16"  # (numpy has no such type: the name stands for it)
 # k_lanc2h's (SRC, OUT) pairs: every one but float -> float
 LANC2H_PAIRS = [(a, b) for a in (np.float16, BF16, np.float32)
@@ -109,6 +109,17 @@ def gen_case(rng, family, big):
         sw, sh = nw * d, nh * e
         ch, tin, tout = 4, np.float32, (np.float32 if rng.rand() < 0.8 else
                                         types[rng.randint(0, 2)])
+    elif family == "dnfh":
+        # whole-ratio downsizing of RGBA frames with half / bfloat16 pixels on
+        # a side: k_dnfh, every (SRC, OUT) pair and the integer output stage
+        # behind a 16-bit source
+        lanc = False
+        d, e = int(rng.choice([2, 3])), int(rng.choice([2, 3]))
+        nw, nh = max(64, sw // d), max(64, sh // e)
+        sw, sh = nw * d, nh * e
+        ch = 4
+        pairs = LANC2H_PAIRS + [(np.float16, np.uint8), (BF16, np.uint16)]
+        tin, tout = pairs[rng.randint(0, len(pairs))]
     elif family in ("gpass_up", "gf"):
         # AVIR upsizing, general ratios: k_gh + k_gv below 7 Mpixels of output,
         # the fused k_gf from there on (float RGBA)
@@ -200,10 +211,9 @@ def main():
                 r = avir_amd.CLancIR()
                 p = r.plan(sw, sh, nw, nh, ch, None, code(tin), code(tout))
             else:
-                r = avir_amd.CImageResizer(8 if tout == np.uint8 else 16)
-                p = r.plan(sw, sh, nw, nh, ch, 0.0, None,
-                           avir_amd._NP2T[np.dtype(tin)],
-                           avir_amd._NP2T[np.dtype(tout)])
+                r = avir_amd.CImageResizer(8 if tout is np.uint8 else 16)
+                p = r.plan(sw, sh, nw, nh, ch, 0.0, None, code(tin),
+                           code(tout))
         return r, p
 
     def run(L, p, ds, shape, tt):
