@@ -1125,7 +1125,20 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 		// odd( m+2 ) start on this row (0 + product), even( m-8 ) and
 		// odd( m-9 ) are complete after it: output rows y0 + 2 and y0 + 1.
 		// MODE 2: first 24 rows of the chunk (row j = g of the chunk: sums of
-		// rows before the chunk are neither updated nor stored). One code
+		// rows before the chunk are neither updated nor stored).
+		// MODE 3 (U2_TAIL, up2_chunks.h): the chunk's last step, from the
+		// fourth step on. The step's last row carries m = qe + 8, where
+		// 2 * qe = yb + 16 is the first output row after the step, so row rr
+		// carries m = qe + 1 + rr, and even( m+3-t ) / odd( m-9+t ) are output
+		// rows below 2 * qe only for t >= rr + 5 / t <= 7 - rr. The other sums
+		// are rows of the chunk above: neither updated nor started (68 + 60
+		// adds, 36 multiplies whose two sums are both unwanted: 124 packed
+		// instructions of the steady 288 remain), row yb + 16 has no store,
+		// and no H1 is woven in: there is no next step to read it. A chunk
+		// that the frame's end clips (by fewer than 8 row pairs) needs no case
+		// of its own: its end lies before 2 * qe, so the rule only keeps more
+		// than needed. So with bands and windows: ylo / yhi clip the stores,
+		// not the march. One code
 		// variant per ring phase: whether a row is stored is one scalar bit
 		// test, and lanes right of the image carry an out-of-range buffer
 		// offset (the hardware drops their stores).
@@ -1229,6 +1242,9 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 			}
 		};
 
+		// (a row's products and the sums they go to, by MODE: `vinterp`)
+#include "up2_vt.inl"
+
 		auto vstep_t = [&]( auto R0C, auto MODEC, const int ub,
 			const bool more )
 		{
@@ -1277,53 +1293,17 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 
 				if( U2_ON( 4 ))
 				{
-#pragma unroll
-					for( int t = 0; t < 12; t += 2 )
-					{
-						// in the chunk's first rows (MODE 2, row j = g): even
-						// sums wanted for t <= j - 6, odd sums for t >= 18 - j
-						const bool we0 = ( MODE != 2 || t <= g - 6 );
-						const bool wo0 = ( MODE != 2 || t >= 18 - g );
-						const bool we1 = ( MODE != 2 || t + 1 <= g - 6 );
-						const bool wo1 = ( MODE != 2 || t + 1 >= 18 - g );
-						f2 p0, p1;
-
-						if( we0 || wo0 ) p0 = V.fe( t ) * c2;
-						if( we1 || wo1 ) p1 = V.fe( t + 1 ) * c2;
-
-						__builtin_amdgcn_sched_barrier( 0 );
-
-						if( we0 )
-						{
-							f2& a = ea[ ( g + 3 - t + 24 ) % 12 ];
-							a = ( t == 0 ? (f2) 0.0f : a ) + p0;
-						}
-
-						if( wo0 )
-						{
-							f2& a = oa[ ( g + 3 + t ) % 12 ];
-							a = a + p0;
-						}
-
-						if( we1 )
-						{
-							f2& a = ea[ ( g + 2 - t + 24 ) % 12 ];
-							a = a + p1;
-						}
-
-						if( wo1 )
-						{
-							f2& a = oa[ ( g + 4 + t ) % 12 ];
-							a = ( t + 1 == 11 ? (f2) 0.0f : a ) + p1;
-						}
-
-						__builtin_amdgcn_sched_barrier( 0 );
-					}
-
+					vinterp( MODEC, V, c2, g, rr );
 					// pin the 24 sums here: the instruction-selection DAG is
 					// free to postpone an add until its sum is next used (a
 					// row later), keeping the product alive instead -- that
 					// spilled ~300 registers
+					// (the pruned tail pins the sums it still wants one by
+					// one, in vinterp: pinned together, the unwanted ones keep
+					// their registers to the end, and two of the three tail
+					// bodies spilled 9 to 13 VGPRs)
+					if constexpr( MODE != 3 || U2_TAIL < 2 )
+					{
 					asm volatile( "" : "+v"( ea[ 0 ]), "+v"( ea[ 1 ]),
 						"+v"( ea[ 2 ]), "+v"( ea[ 3 ]), "+v"( ea[ 4 ]),
 						"+v"( ea[ 5 ]), "+v"( ea[ 6 ]), "+v"( ea[ 7 ]),
@@ -1334,9 +1314,12 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 						"+v"( oa[ 5 ]), "+v"( oa[ 6 ]), "+v"( oa[ 7 ]),
 						"+v"( oa[ 8 ]), "+v"( oa[ 9 ]), "+v"( oa[ 10 ]),
 						"+v"( oa[ 11 ]));
+					}
 
 					const f2 od = oa[ ( g + 3 ) % 12 ]; // odd( m-9 ): row y0 + 1
 					const f2 ed = ea[ ( g + 4 ) % 12 ]; // even( m-8 ): row y0 + 2
+					// (the pruned tail's last even row is no row of the chunk)
+					const bool est = ( MODE != 3 || U2_TAIL < 2 || rr + 1 < U2_RB );
 
 					if( MODE != 2 || g >= 17 )
 					{
@@ -1350,6 +1333,7 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 							store_io( od, __builtin_amdgcn_make_buffer_rsrc(
 								dbase, 0, ( rmask & ( 1u << ( 2 * rr )) ?
 								0x7fffffff : 0 ), 0x00020000 ), so + drow_b );
+							if( est )
 							store_io( ed, __builtin_amdgcn_make_buffer_rsrc(
 								dbase, 0, ( rmask & ( 2u << ( 2 * rr )) ?
 								0x7fffffff : 0 ), 0x00020000 ), so + 2 * drow_b );
@@ -1365,7 +1349,7 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 								0x00020000 ), dlane_v, so + drow_b, U2_STAUX );
 						}
 
-						if( U2_ON( 1 ) || ed.y == 1234.5f )
+						if( est && ( U2_ON( 1 ) || ed.y == 1234.5f ))
 						{
 							__builtin_amdgcn_raw_buffer_store_b64(
 								__builtin_bit_cast( u2, ed ),
@@ -1384,10 +1368,10 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 				asm volatile( "" : "+s"( so ));
 
 				// ---- H1 of the next step, one iteration
-				// (unconditional: after the chunk's last step it works on
-				// stale tiles and nobody reads its result)
+				// (MODE 3 has no next step; a last step in another mode works
+				// on stale tiles and nobody reads its result)
 				if( rr % H1EVERY == 0 && rr / H1EVERY < NH1 && U2_ON( 2 ) &&
-					U2_ABL_H1( rr / H1EVERY ) && U2_ABL_TAIL())
+					U2_ABL_H1( rr / H1EVERY ) && U2_ABL_TAIL() && MODE != 3 )
 				{
 					h1_iter_p( rr / H1EVERY, hv );
 				}
@@ -1397,15 +1381,18 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 		typedef std::integral_constant< int, 0 > I0;
 		typedef std::integral_constant< int, 1 > I1;
 		typedef std::integral_constant< int, 2 > I2;
+		typedef std::integral_constant< int, 3 > I3;
 		typedef std::integral_constant< int, 8 > I8;
 		typedef std::integral_constant< int, 16 > I16;
 
 		// one marching step: interval B = {DMA of the next S tile, H2 of this
-		// step}, interval A = {V of this step, H1 of the next} (see march)
-		auto march_t = [&]( auto R0C, auto RAMPC, const int sb )
+		// step}, interval A = {V of this step, H1 of the next} (see march).
+		// MODE 3 is the chunk's last step by construction: no next tile.
+		auto march_t = [&]( auto R0C, auto MODEC, const int sb )
 		{
 			const int ub = u0 + sb;
-			const bool more = ( sb + U2_RB < nsteps );
+			const bool more = ( decltype( MODEC )::value != 3 &&
+				sb + U2_RB < nsteps );
 #ifdef U2_DBG
 			// (bit 32: H2 of the chunk's last two steps and the H1 that feeds
 			// them -- woven into the step before -- are skipped)
@@ -1448,41 +1435,54 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 			u2_setprio( U2_PRIO_V );
 #endif
 
-			if( decltype( RAMPC )::value )
-			{
-				vstep_t( R0C, I2(), ub, more );
-			}
-			else
-			{
-				vstep_t( R0C, I1(), ub, more );
-			}
-
+			vstep_t( R0C, MODEC, ub, more );
 			U2_SYNC();
 		};
 
 		// the chunk's first 24 rows (nsteps >= 24: cq >= 6), then the period
 		// of 24 rows = 3 steps per trip
-		march_t( I0(), std::true_type(), 0 );
-		march_t( I8(), std::true_type(), 8 );
-		march_t( I16(), std::true_type(), 16 );
+		march_t( I0(), I2(), 0 );
+		march_t( I8(), I2(), 8 );
+		march_t( I16(), I2(), 16 );
 
-		for( int sb = 24; sb < nsteps; sb += 24 )
+		// U2_TAIL: the loop leaves the chunk's last step to the tail bodies
+		// behind it, one per ring phase. Inside the loop -- as one arm of a
+		// branch after H2, or as a whole step that breaks out -- the tail
+		// cost every instance 60 to 177 spilled VGPRs: the loop holds
+		// lane-dependent branches, so its control flow is made structured as
+		// a whole, the way out becomes a flag, and the sums stay live on a
+		// path from the tail back into the loop that is never taken.
+		constexpr int LAST = ( U2_TAIL >= 1 ? U2_RB : 0 );
+
+		for( int sb = 24; sb + LAST < nsteps; sb += 24 )
 		{
-			march_t( I0(), std::false_type(), sb );
+			march_t( I0(), I1(), sb );
 
-			if( sb + 8 >= nsteps )
+			if( sb + 8 + LAST >= nsteps )
 			{
 				break;
 			}
 
-			march_t( I8(), std::false_type(), sb + 8 );
+			march_t( I8(), I1(), sb + 8 );
 
-			if( sb + 16 >= nsteps )
+			if( sb + 16 + LAST >= nsteps )
 			{
 				break;
 			}
 
-			march_t( I16(), std::false_type(), sb + 16 );
+			march_t( I16(), I1(), sb + 16 );
+		}
+
+		if( U2_TAIL >= 1 && nsteps > 24 )
+		{
+			const int sbl = ( nsteps - 1 ) & ~( U2_RB - 1 ); // the last step
+
+			switch(( sbl >> 3 ) % 3 )
+			{
+				case 0: march_t( I0(), I3(), sbl ); break;
+				case 1: march_t( I8(), I3(), sbl ); break;
+				default: march_t( I16(), I3(), sbl );
+			}
 		}
 	}
 	else

@@ -35,6 +35,40 @@ constexpr int up2_chunk_rows( const int c, const int cq, const int nlong )
 	return( c < nlong ? cq + U2_RB : cq );
 }
 
+// U2_TAIL: what the transposed form (k_up2< true >) does in a chunk's last
+// marching step, from the fourth step on -- 2: no dead vertical sums and no
+// woven H1, 1: no woven H1 only, 0: the steady body (for A/B builds).
+#ifndef U2_TAIL
+#define U2_TAIL 2
+#endif
+
+// Which running sums want tap t's product of a row (up2_vt.inl), by the mode
+// of the row's marching step. Row g of the ring, row rr of its step, carries
+// C2[ m ]; the product goes to even( m+3-t ) and to odd( m-9+t ).
+//   1 steady: both, always.
+//   2 the chunk's first 24 rows (row j = g of the chunk): sums of rows before
+//     the chunk are left alone -- even for t <= j - 6, odd for t >= 18 - j.
+//   3 the chunk's last step: its last row carries m = qe + 8, where 2 * qe is
+//     the first output row after the step, so row rr carries m = qe + 1 + rr.
+//     Sums of the rows from 2 * qe on are left alone: even( m+3-t ) lies below
+//     qe for t >= rr + 5, odd( m-9+t ) for t <= 7 - rr. Per thread that leaves
+//     64 of the 192 adds and 60 of the 96 multiplies of a step (a product is
+//     computed iff one of its sums wants it). A chunk that the frame's end
+//     clips ends before 2 * qe: the rule keeps more than it needs, never less.
+constexpr bool up2_want_even( const int mode, const int g, const int rr,
+	const int t )
+{
+	return( mode == 2 ? t <= g - 6 :
+		( mode == 3 && U2_TAIL >= 2 ? t >= rr + 5 : true ));
+}
+
+constexpr bool up2_want_odd( const int mode, const int g, const int rr,
+	const int t )
+{
+	return( mode == 2 ? t >= 18 - g :
+		( mode == 3 && U2_TAIL >= 2 ? t <= 7 - rr : true ));
+}
+
 // (the chunk that holds source row q)
 constexpr int up2_chunk_of( const int q, const int cq, const int nlong )
 {
