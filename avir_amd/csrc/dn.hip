@@ -610,6 +610,13 @@ int dn_run_h( void* d, const void* src, int src_type, int src_ch, long src_ss,
 	const int seg = 64 * R - 6;
 	const dim3 grid(( D -> h.out_len + seg - 1 ) / seg, ( b - a + 3 ) / 4 );
 
+	// (a workgroup is four waves, a source row each)
+	if( getenv( "AVIRHIP_VERBOSE" ) != nullptr )
+	{
+		fprintf( stderr, "k_dnh: %u items (strips %u, chunk %d)\n",
+			grid.x * grid.y, grid.x, 4 );
+	}
+
 	if( D -> h.K == 3 )
 	{
 		hipLaunchKernelGGL(( k_dnh< 3, 38, 3 > ), grid, dim3( 256 ), 0, st, P );
@@ -651,6 +658,14 @@ int dn_run_v( void* d, const float* flt, long flt_ss, int width, float* dst,
 	}
 
 	const dim3 grid(( width + 63 ) / 64, ( P.g_hi - P.g_lo + 3 ) / 4 );
+
+	// (a workgroup is four waves, a group of RO output rows each: the groups
+	// lie on the frame's grid, whichever band is asked for)
+	if( getenv( "AVIRHIP_VERBOSE" ) != nullptr )
+	{
+		fprintf( stderr, "k_dnv: %u items (strips %u, chunk %d)\n",
+			grid.x * grid.y, grid.x, RO );
+	}
 
 	if( D -> v.K == 3 )
 	{

@@ -756,12 +756,9 @@ int dn_run_hv( void* d, const float* src, long src_ss, float* dst, int row0,
 	static int dcalls = 0;
 
 
-	// one workgroup per compute unit: a chunk's warm-up (NT + 5K source rows)
-	// is paid per work item, so as few, as tall chunks as fill the chip
 	P.nstrips = ( D -> h.out_len + DF_W - 1 ) / DF_W;
 	const int rows = row1 - row0;
-	const int want = std::max( 1, D -> ncu / P.nstrips );
-	P.crows = std::max( 8, ( rows + want - 1 ) / want );
+	P.crows = dnf_chunk_rows( rows, D -> ncu, P.nstrips );
 	P.nchunks = ( rows + P.crows - 1 ) / P.crows;
 	const dim3 grid( P.nstrips * P.nchunks );
 
@@ -807,6 +804,7 @@ int dn_run_hv( void* d, const float* src, long src_ss, float* dst, int row0,
 	}
 
 #undef DF_LAUNCH
+	dnf_verbose( "k_dnf", P.nstrips, P.nchunks, P.crows );
 
 	if(( dbg & 16 ) && P.clk != nullptr && ++dcalls == 100 )
 	{
@@ -1486,8 +1484,7 @@ int dn_run_hv16( void* d, const ImageRef& src, float* dst, int row0, int row1,
 	// (dn_run_hv's chunk rule)
 	P.nstrips = ( D -> h.out_len + DF_W - 1 ) / DF_W;
 	const int rows = row1 - row0;
-	const int want = std::max( 1, D -> ncu / P.nstrips );
-	P.crows = std::max( 8, ( rows + want - 1 ) / want );
+	P.crows = dnf_chunk_rows( rows, D -> ncu, P.nstrips );
 	P.nchunks = ( rows + P.crows - 1 ) / P.crows;
 	const dim3 grid( P.nstrips * P.nchunks );
 
@@ -1519,6 +1516,7 @@ int dn_run_hv16( void* d, const ImageRef& src, float* dst, int row0, int row1,
 
 #undef DH_FORM
 #undef DH_LAUNCH
+	dnf_verbose( "k_dnfh", P.nstrips, P.nchunks, P.crows );
 
 	AVIRHIP_HIPCHECK( hipGetLastError() );
 	return( AVIRHIP_OK );

@@ -204,6 +204,38 @@ __device__ __forceinline__ void df_wait( DfBatch< B >& d )
 	}
 }
 
+// ---- host side: the chunk rule of dn_run_hv / dn_run_hv16 (dnf.hip)
+
+// Output rows per chunk of a band of `rows` rows. One workgroup per compute
+// unit: a chunk's warm-up (NT + 5K source rows) is paid per work item, so as
+// few, as tall chunks as fill the chip. AVIRHIP_DNF_CROWS (read per call:
+// sweeps and the seam tests) forces a height, any number of rows >= 1 as it
+// is: the kernels clip a chunk's stores to its own rows and march in steps of
+// source rows, so no multiple of anything is required of it.
+static inline int dnf_chunk_rows( const int rows, const int ncu, const int nstrips )
+{
+	const int want = std::max( 1, ncu / nstrips );
+	const char* const e = getenv( "AVIRHIP_DNF_CROWS" );
+
+	if( e != nullptr )
+	{
+		return( std::max( 1, atoi( e )));
+	}
+
+	return( std::max( 8, ( rows + want - 1 ) / want ));
+}
+
+// the launchers' line under AVIRHIP_VERBOSE (read per call)
+static inline void dnf_verbose( const char* const name, const int nstrips,
+	const int nchunks, const int crows )
+{
+	if( getenv( "AVIRHIP_VERBOSE" ) != nullptr )
+	{
+		fprintf( stderr, "%s: %d items (strips %d, crows %d)\n", name,
+			nstrips * nchunks, nstrips, crows );
+	}
+}
+
 } // namespace avirhip
 
 #endif

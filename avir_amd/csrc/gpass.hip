@@ -1281,6 +1281,12 @@ static int run_h( const GPData* D, const GPPass& G, hipStream_t st )
 
 		if( launch_gh2( P, items2, lds2, st ) == 0 )
 		{
+			if( getenv( "AVIRHIP_VERBOSE" ) != nullptr )
+			{
+				fprintf( stderr, "k_gh2: %d items (strips %d, chunk %d)\n",
+					items2, P.nstrips, P.chunk );
+			}
+
 			AVIRHIP_HIPCHECK( hipGetLastError() );
 			return( AVIRHIP_OK );
 		}
@@ -1314,6 +1320,12 @@ static int run_h( const GPData* D, const GPPass& G, hipStream_t st )
 	const int nch = ( rows + P.chunk - 1 ) / P.chunk;
 	const int items = P.nstrips * nch;
 	const size_t lds = lds_h;
+
+	if( getenv( "AVIRHIP_VERBOSE" ) != nullptr )
+	{
+		fprintf( stderr, "k_gh: %d items (strips %d, chunk %d)\n", items,
+			P.nstrips, P.chunk );
+	}
 	const GPAxis& A = P.ax;
 
 	if( A.lanc )
@@ -1632,7 +1644,17 @@ static int run_lanc_fused( const avirhip_plan* p, const GPData* D,
 		G.lout = gp_make_lout( p, *C.lout );
 	}
 
-	return( lfuse_launch( G, C.st ));
+	const int rc = lfuse_launch( G, C.st );
+
+	// (lfuse_launch leaves the chunk it chose in G)
+	if( rc == AVIRHIP_OK && getenv( "AVIRHIP_VERBOSE" ) != nullptr )
+	{
+		fprintf( stderr, "k_lf: %d items (strips %d, chunk %d)\n", G.nstrips *
+			(( G.row_hi - G.row_lo + G.chunk - 1 ) / G.chunk ), G.nstrips,
+			G.chunk );
+	}
+
+	return( rc );
 }
 
 // LANCIR, vertical first (lancir.h:601-646): mid = [new_h][src_w], only the

@@ -177,6 +177,13 @@ int gpass_run_v( const GPAxis& A_, int v_blk, int v_rs, int v_rc,
 
 	const int nch = ( rows + P.chunk - 1 ) / P.chunk;
 	const int items = P.nstrips * nch;
+
+	if( getenv( "AVIRHIP_VERBOSE" ) != nullptr )
+	{
+		fprintf( stderr, "k_gv: %d items (strips %d, chunk %d, clamp %d, nt %d, "
+			"post %d)\n", items, P.nstrips, P.chunk, maxg - gextra, P.ax.nt,
+			( gextra != 0 ? 1 : 0 ));
+	}
 	const size_t lds = (size_t) ( P.rs + P.rc ) * rowb + GV_QB +
 		(size_t) ( P.chunk + gextra ) * ( ntp * 4 + 4 ) + 64;
 

@@ -675,6 +675,12 @@ int lanc2_run( const avirhip_plan* p, const float* src, float* dst, int row0,
 	const int chunk1 = ( row1 - 1 ) / cr;
 	const int items = P.nstrips * ( chunk1 - P.chunk0 + 1 );
 
+	if( getenv( "AVIRHIP_VERBOSE" ) != nullptr )
+	{
+		fprintf( stderr, "k_lanc2: %d items (strips %d, cq %d, chunk0 %d)\n",
+			items, P.nstrips, P.cq, P.chunk0 );
+	}
+
 #define L2_LAUNCH( IOK, SK ) { if( p -> l_order == 3 ) \
 		hipLaunchKernelGGL(( k_lanc2< IOK, SK, 3 > ), dim3( items ), \
 		dim3( L2_NT ), 0, st, P ); else \

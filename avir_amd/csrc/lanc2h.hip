@@ -376,11 +376,25 @@ int lanc2h_run( const avirhip_plan* q, const ImageRef& src,
 		}
 	}
 
+	// (k_lanc2's knob and rounding, read per call: sweeps and the seam tests)
+	const char* ecq = getenv( "AVIRHIP_LANC2_CQ" );
+
+	if( ecq != nullptr && atoi( ecq ) >= 2 )
+	{
+		cq = (( atoi( ecq ) + 6 + LH_RB - 1 ) / LH_RB ) * LH_RB - 6;
+	}
+
 	P.cq = cq;
 	const int cr = cq * 2;
 	P.chunk0 = row0 / cr;
 	const int chunk1 = ( row1 - 1 ) / cr;
 	const int items = P.nstrips * ( chunk1 - P.chunk0 + 1 );
+
+	if( getenv( "AVIRHIP_VERBOSE" ) != nullptr )
+	{
+		fprintf( stderr, "k_lanc2h: %d items (strips %d, cq %d, chunk0 %d)\n",
+			items, P.nstrips, P.cq, P.chunk0 );
+	}
 
 #define LH_LAUNCH( SK, OK ) hipLaunchKernelGGL(( k_lanc2h< SK, OK > ), \
 		dim3( items ), dim3( LH_NT ), 0, st, P )

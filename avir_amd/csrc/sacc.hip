@@ -2250,6 +2250,15 @@ int sacc_run_axis( const SAData* D, const SAPass& G, const SAForm& F,
 		return( 1 );
 	}
 
+	// (pass h: the lanes are image rows, a chunk is a run of outputs along x;
+	// pass v: the lanes are pixels of a row, a chunk is a run of output rows)
+	if( getenv( "AVIRHIP_VERBOSE" ) != nullptr )
+	{
+		fprintf( stderr, "%s: %d items (strips %d, chunk %d, pass %c)\n",
+			( !two ? "k_sacc" : ( !rows || two_hf ? "k_sacc2v" : "k_sacc2" )),
+			items, P.nstrips, P.chunk, ( rows ? 'h' : 'v' ));
+	}
+
 	if( two )
 	{
 		if( !rows )

@@ -544,6 +544,12 @@ int up64_run_h( const avirhip_plan* p, const void* src, const int src_type,
 	const int nchunks = ( rows + crows - 1 ) / crows;
 	const dim3 grid( (unsigned) ( P.nstrips * nchunks ));
 
+	if( getenv( "AVIRHIP_VERBOSE" ) != nullptr )
+	{
+		fprintf( stderr, "k_uh64: %d items (strips %d, crows %d, rh %d)\n",
+			P.nstrips * nchunks, P.nstrips, P.crows, rh );
+	}
+
 #define UHR( CH, T, R ) do { (void) AVIRHIP_DYN_LDS(( k_uh64< CH, T, R > ), lds ); \
 	hipLaunchKernelGGL(( k_uh64< CH, T, R > ), grid, dim3( 256 ), lds, st, P ); \
 	} while( 0 )
@@ -614,6 +620,13 @@ int up64_run_v( const avirhip_plan* p, const double* fltbuf, void* dst,
 	P.O.crows = std::max( 48, ( rows + want - 1 ) / want );
 	const int nchunks = ( rows + P.O.crows - 1 ) / P.O.crows;
 	const dim3 grid( (unsigned) ((( P.ngroups + 3 ) / 4 ) * nchunks ));
+
+	// (a workgroup is four waves, a group of 64 lanes each)
+	if( getenv( "AVIRHIP_VERBOSE" ) != nullptr )
+	{
+		fprintf( stderr, "k_uv64: %u items (strips %d, crows %d, epl %d)\n",
+			grid.x, P.ngroups, P.O.crows, epl );
+	}
 
 #define UV( E, T ) hipLaunchKernelGGL(( k_uv64< E, T > ), grid, dim3( 256 ), 0, \
 	st, P )

@@ -43,7 +43,7 @@ import numpy as np  # noqa: E402
 
 CHUNK_ENVS = ("AVIRHIP_GV_CHUNK", "AVIRHIP_GH_CHUNK", "AVIRHIP_GF_CHUNK",
               "AVIRHIP_LF_CHUNK", "AVIRHIP_SA_CHUNK", "AVIRHIP_UP2_CQ",
-              "AVIRHIP_LANC2_CQ")
+              "AVIRHIP_LANC2_CQ", "AVIRHIP_DNF_CROWS")
 FAMILIES = ("all", "up2", "lanc2", "lanc2h", "dnf", "dnfh", "gpass_up", "gf",
             "lf", "lanc_dn", "sacc")
 BF16 = "bfloat16"  # (numpy has no such type: the name stands for it)
@@ -243,6 +243,7 @@ def main():
                       "AVIRHIP_LF_CHUNK"):
                 os.environ[e] = str(c)
             os.environ["AVIRHIP_SA_CHUNK"] = str(max(8, 2 * c))
+            os.environ["AVIRHIP_DNF_CROWS"] = str(c)
             cq = int(rng.choice([6, 14, 22, 30, 46, 70, 134]))
             os.environ["AVIRHIP_UP2_CQ"] = str(cq)
             os.environ["AVIRHIP_LANC2_CQ"] = str(cq)
