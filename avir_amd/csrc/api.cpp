@@ -597,9 +597,10 @@ void need_range( const LOp& op, int a, int b, int& ia, int& ib )
 }
 
 // The float copies a call may need, allocated up front: every road but
-// k_dnfh's (avir_dn16) calls this first. That road skips it, and avir_pack
-// (`packed`) and avir_need_res (`resbuf`) allocate each when something is about
-// to use it -- the same sizes as here, so after this function they are no-ops.
+// k_dnfh's (avir_dn16) and the pass kernels' with half / bfloat16 pixels on a
+// side (exec_avir) calls this first. Those skip it, and avir_pack (`packed`)
+// and avir_need_res (`resbuf`) allocate each when something is about to use it
+// -- the same sizes as here, so after this function they are no-ops.
 static int ensure_scratch( avirhip_plan* p )
 {
 	int rc;
@@ -1181,12 +1182,23 @@ static int avir_fast( avirhip_plan* p, const int path, AvirSrc& S, void* dst,
 	// integer / narrow output without gamma / error diffusion: the last pass
 	// may convert and store into the caller's image itself (no float result,
 	// no epilogue pass)
-	// (half / bfloat16 pixels: the marching kernel alone narrows and stores
-	// them; behind every other path the output stage does)
+	// (half / bfloat16 pixels: the marching kernel (4) and the last pass of
+	// the pass kernels (5, 1-4 channels: gp_store_int_row) narrow and store
+	// them; behind the tiles the output stage does)
+	const bool io16 = ( path == 5 && gpass_io16() );
 	const bool stores = ( !direct && !p -> gamma &&
 		(( p -> dither == AVIRHIP_DITHER_DEF && int_out ) ||
 		p -> out_type == AVIRHIP_F32 ||
-		( dtype_is_float16_kind( p -> out_type ) && path == 4 )) && fio );
+		( dtype_is_float16_kind( p -> out_type ) && ( path == 4 || io16 ))) &&
+		fio );
+	// a half / bfloat16 source k_gh's typed loader takes (path 5): elements
+	// are loaded whole, four at a time -- a base that is a multiple of their
+	// size, at least four of them up to the end of the last source row the
+	// band's first pass reads (run_h's `raw_elems`); any row pitch
+	const bool raw16 = ( io16 && dtype_is_float16_kind( p -> in_type ) &&
+		( (uintptr_t) S.img & 1 ) == 0 && row1 > row0 &&
+		(long) gpass_last_src_row( p, row0, row1 ) * p -> src_stride +
+		(long) p -> src_w * p -> io_ch >= 4 );
 	// half RGBA on both sides, or bfloat16 RGBA on both sides: the marching
 	// kernel reads the elements as they lie
 	const bool half_io = ( dtype_is_float16_kind( p -> in_type ) &&
@@ -1198,7 +1210,7 @@ static int avir_fast( avirhip_plan* p, const int path, AvirSrc& S, void* dst,
 	// kernel (4) when it also stores the caller's integer pixels (it may still
 	// refuse the call -- alignment, a source window: the pack pass runs then)
 	const bool raw = ( !p -> gamma && p -> ch == 4 && ( path == 5 ?
-		S.need_pack && ( int_in || p -> in_type == AVIRHIP_F32 ) &&
+		S.need_pack && ( int_in || p -> in_type == AVIRHIP_F32 || raw16 ) &&
 		gpass_takes_raw( p ) :
 		path == 4 ? S.need_pack && (( int_in &&
 		( p -> io_ch == 3 || p -> io_ch == 4 ) && int_out ) || half_io ) &&
@@ -1257,6 +1269,11 @@ static int avir_fast( avirhip_plan* p, const int path, AvirSrc& S, void* dst,
 
 		for( ;; )
 		{
+			// (calls with 16-bit pixels come without ensure_scratch, exec_avir:
+			// the float result is made when a pass is about to write it)
+			if( iout == nullptr &&
+				( rc = avir_need_res( p, fdst, direct )) != 0 ) return( rc );
+
 			rc = ( raw ?
 				gpass_run( p, nullptr, 0, fdst, row0, row1, st, &img, iout,
 				nullptr ) :
@@ -1361,7 +1378,13 @@ static int exec_avir( avirhip_plan* p, const void* src, void* dst, int row0,
 	const int path = ( p -> path != 0 ? p -> path : p -> auto_path );
 	// (k_dnfh's road makes neither float copy: avir_pack and avir_need_res
 	// allocate them where a refused call needs them after all)
-	int rc = ( avir_dn16( p, path ) ? AVIRHIP_OK : ensure_scratch( p ));
+	// (nor does a call of the pass kernels with 16-bit pixels on a side, whose
+	// first pass may read and whose last pass may store them: avir_fast)
+	const bool gp16 = ( path == 5 && !p -> gamma && gpass_io16() &&
+		( dtype_is_float16_kind( p -> in_type ) ||
+		dtype_is_float16_kind( p -> out_type )));
+	int rc = ( avir_dn16( p, path ) || gp16 ? AVIRHIP_OK :
+		ensure_scratch( p ));
 	if( rc != 0 ) return( rc );
 
 	const bool need_pack = ( p -> gamma || p -> in_type != AVIRHIP_F32 ||

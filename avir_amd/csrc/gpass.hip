@@ -1182,7 +1182,8 @@ static void launch_gh2( const GHParams& P, int items, size_t lds,
 		dim3( 64 ), lds, st, P );
 }
 
-// src_kind: 0 float RGBA (LDS-DMA); 1 uint8, 2 uint16, 3 float pixels read raw
+// src_kind: 0 float RGBA (LDS-DMA); 1 uint8, 2 uint16, 3 float, 4 half,
+// 5 bfloat16 pixels read raw
 // (LANCIR plans: 1 / 2 = the output stage stores uint8 RGB / RGBA pixels)
 template< int MODE, bool LANC >
 static void launch_gh( const GHParams& P, int src_kind, int items, size_t lds,
@@ -1194,8 +1195,26 @@ static void launch_gh( const GHParams& P, int src_kind, int items, size_t lds,
 		case 2: launch_gh2< MODE, LANC, 2 >( P, items, lds, st ); break;
 		case 3: launch_gh2< MODE, LANC, ( LANC ? 0 : 3 ) >( P, items, lds, st );
 			break;
+		case 4: launch_gh2< MODE, LANC, ( LANC ? 0 : 4 ) >( P, items, lds, st );
+			break;
+		case 5: launch_gh2< MODE, LANC, ( LANC ? 0 : 5 ) >( P, items, lds, st );
+			break;
 		default: launch_gh2< MODE, LANC, 0 >( P, items, lds, st ); break;
 	}
+}
+
+// Whether float RGBA rows of this plan's horizontal axis are k_gh2's (run_h;
+// the ONE test behind it and behind the routing of half / bfloat16 sources,
+// io16_prefers_pack): the geometry exists, from AVIRHIP_GH2_MIN_NT taps (22),
+// not AVIRHIP_NO_GH2. (Read per call: the GPU suite runs every form on every
+// tap count.)
+static bool gh2_wanted( const GPData* D )
+{
+	const int gh2_min_nt = ( getenv( "AVIRHIP_GH2_MIN_NT" ) != nullptr ?
+		atoi( getenv( "AVIRHIP_GH2_MIN_NT" )) : 22 );
+
+	return( D -> h2_ow != 0 && D -> h.a.nt >= gh2_min_nt &&
+		getenv( "AVIRHIP_NO_GH2" ) == nullptr );
 }
 
 // One horizontal gather pass (k_gh, k_gh2). 1: the pass cannot read `G.raw`.
@@ -1228,7 +1247,9 @@ static int run_h( const GPData* D, const GPPass& G, hipStream_t st )
 	{
 		P.raw = raw -> ptr; P.raw_ss = raw -> stride; P.raw_ch = raw -> ch;
 		src_kind = ( raw -> type == AVIRHIP_U8 ? 1 :
-			( raw -> type == AVIRHIP_U16 ? 2 : 3 ));
+			( raw -> type == AVIRHIP_U16 ? 2 :
+			( raw -> type == AVIRHIP_F16 ? 4 :
+			( raw -> type == AVIRHIP_BF16 ? 5 : 3 ))));
 		P.raw_elems = (long) ( row_hi - 1 ) * raw -> stride +
 			(long) G.src_w * raw -> ch;
 
@@ -1253,13 +1274,8 @@ static int run_h( const GPData* D, const GPPass& G, hipStream_t st )
 	// (reads 2.6 M -> 1.6 M, bank conflicts 7.2 M -> 0.2 M cycles per launch),
 	// which binds at k = 1.9 (lanes 30 bytes apart) and not at k = 1.5, where
 	// its half as many, twice as long waves cost more than they save.
-	// AVIRHIP_NO_GH2 / AVIRHIP_GH2_MIN_NT: A/B.
-	// (read per call: the GPU suite runs every form on every tap count)
-	const int gh2_min_nt = ( getenv( "AVIRHIP_GH2_MIN_NT" ) != nullptr ?
-		atoi( getenv( "AVIRHIP_GH2_MIN_NT" )) : 22 );
-
-	if( D -> h2_ow != 0 && raw == nullptr && G.lout == nullptr &&
-		P.ax.nt >= gh2_min_nt && getenv( "AVIRHIP_NO_GH2" ) == nullptr )
+	// AVIRHIP_NO_GH2 / AVIRHIP_GH2_MIN_NT: A/B (gh2_wanted).
+	if( gh2_wanted( D ) && raw == nullptr && G.lout == nullptr )
 	{
 		P.nstrips = D -> h2_nstrips; P.ow = D -> h2_ow;
 		P.seg = D -> d_h2seg; P.nseg = D -> h2_nseg;
@@ -1379,6 +1395,21 @@ static void v_source_rows( const GPData* D, int row0, int row1, int& a, int& b )
 	b = std::max( 0, std::min( b, A.in_len - 1 ));
 }
 
+// The last source row the first pass of output rows [row0, row1) of an AVIR plan
+// reads: run_h's `row_hi - 1`, which bounds a typed source's `raw_elems`.
+int gpass_last_src_row( const avirhip_plan* p, int row0, int row1 )
+{
+	const GPData* D = (const GPData*) p -> gpass;
+	int a = 0, b = p -> src_h - 1;
+
+	if( D != nullptr && !p -> is_lancir && row1 > row0 )
+	{
+		v_source_rows( D, row0, row1, a, b );
+	}
+
+	return( b );
+}
+
 // LANCIR (an inner plan): whether its vertical pass -- the first one -- reads
 // the owner's integer / narrower image as it is (whole-pixel lanes of the
 // register-window variants of k_gv: gpass_v_raw_ok).
@@ -1396,14 +1427,94 @@ bool gpass_lancir_takes_raw( const avirhip_plan* p, const ImageRef& img )
 
 // Whether the first pass reads the caller's image as it is (integer types,
 // 1-4 channels): AVIR plans whose horizontal axis streams (sacc.hip).
+//
+// Half / bfloat16 sources (1-4 channels): k_gh's typed loader alone knows them
+// (gp_load_raw kinds 4, 5), so the horizontal axis must run the gather kernels
+// with a source segment of at most four pieces and must not be one the
+// accumulation kernels want -- that axis keeps the pack pass, k_sacc* reads
+// uint8, uint16 and float elements only. Two classes of call whose float RGBA
+// kernels have no typed form keep the pack pass as well (io16_prefers_pack).
+// AVIRHIP_GP_NO_IO16 (read per call): the pack pass and the output stage for
+// every 16-bit image on this path -- A/B timing, differential tests.
+bool gpass_io16()
+{
+	return( getenv( "AVIRHIP_GP_NO_IO16" ) == nullptr );
+}
+
+static long gf_minpix()
+{
+	// (a tuning aid, read by the first call of any plan)
+	static const long v = ( getenv( "AVIRHIP_GF_MINPIX" ) != nullptr ?
+		atol( getenv( "AVIRHIP_GF_MINPIX" )) : 7000000L );
+
+	return( v );
+}
+
+// whether route_avir runs k_gf for a float RGBA source (raw == nullptr)
+static bool gf_wanted( const avirhip_plan* p, const GPData* D )
+{
+	const bool two_pass = (( p -> variant & AVIRHIP_VARIANT_UPG_TWO_PASS ) != 0 );
+	// (a forced variant bit 4 = "fused whatever the size": tests)
+	const bool fused = (( p -> variant & AVIRHIP_VARIANT_UPG_FUSED ) != 0 );
+
+	return( D -> h.a.mode == GP_PRE &&
+		D -> v.a.mode == GP_PRE && D -> h.a.nt == 12 && D -> v.a.nt == 12 &&
+		D -> h_geom && !two_pass &&
+		((long) p -> new_w * p -> new_h >= gf_minpix() || fused ) &&
+		getenv( "AVIRHIP_NO_GFUSE" ) == nullptr );
+}
+
+// A half / bfloat16 source where the float RGBA kernel of the call's class has
+// no typed form -- k_gf (large upsizing, AVIRHIP_VARIANT_UPG_FUSED) and k_gh2
+// (1 < k < 2 from 22 taps) read by LDS-DMA only: pack pass + that kernel, or
+// k_gh's typed form ( + k_gv )? The pack pass, both times -- measured in one
+// process, the roads alternating over a ring of buffers, RGBA half in and out
+// with the narrowing store behind either road (tools/half_timing.py --gpass;
+// pack + float RGBA kernel / typed k_gh / both sides unfused, ms):
+//   k_gf   1920x1080 -> 5760x3240   0.128 / 0.140 / 0.200
+//          3840x2160 -> 6144x3456   0.191 / 0.207 / 0.272
+//   k_gh2  3840x2160 -> 2000x1125   0.130 / 0.145 / 0.145
+// (bfloat16 the same within 0.003; spread of repeated runs under 0.002.)
+// k_gf saves more on `mid` than the pack pass costs; the typed POST form is
+// k_gh's any-tap-count variant (190 VGPRs, two waves per SIMD), which loses
+// to k_gh2 what the pack pass costs. AVIRHIP_VARIANT_UPG_FUSED always means
+// k_gf. AVIRHIP_GP_IO16_GF / AVIRHIP_GP_IO16_GH2 = 1 (read per call): the
+// typed road, A/B.
+static bool io16_prefers_pack( const avirhip_plan* p, const GPData* D )
+{
+	if( gf_wanted( p, D ))
+	{
+		const char* const e = getenv( "AVIRHIP_GP_IO16_GF" );
+
+		return(( p -> variant & AVIRHIP_VARIANT_UPG_FUSED ) != 0 ||
+			e == nullptr || atoi( e ) == 0 );
+	}
+
+	if( D -> h.a.mode == GP_POST && gh2_wanted( D ))
+	{
+		const char* const e = getenv( "AVIRHIP_GP_IO16_GH2" );
+
+		return( e == nullptr || atoi( e ) == 0 );
+	}
+
+	return( false );
+}
+
 bool gpass_takes_raw( const avirhip_plan* p )
 {
 	const GPData* D = (const GPData*) p -> gpass;
 	const bool int_src = ( p -> in_type == AVIRHIP_U8 ||
 		p -> in_type == AVIRHIP_U16 );
 
-	// (the loaders know uint8, uint16 and float elements: any other type --
-	// half, bfloat16, double -- goes through the pack pass)
+	if( dtype_is_float16_kind( p -> in_type ))
+	{
+		return( D != nullptr && !p -> is_lancir && !p -> gamma && gpass_io16() &&
+			h_gather_takes( D, true ) && !sa_wanted( D -> sa_h, true, true ) &&
+			!io16_prefers_pack( p, D ));
+	}
+
+	// (the loaders of the accumulation kernels know uint8, uint16 and float
+	// elements: double goes through the pack pass)
 	return( D != nullptr && !p -> is_lancir &&
 		( int_src || p -> in_type == AVIRHIP_F32 ) &&
 		( sa_wanted( D -> sa_h, int_src || ( p -> in_type == AVIRHIP_F32 &&
@@ -1504,12 +1615,9 @@ static GPRoute route_lancir( const avirhip_plan* p, const GPData* D,
 }
 
 static GPRoute route_avir( const avirhip_plan* p, const GPData* D,
-	const ImageRef* raw, const bool has_out, const long gf_minpix )
+	const ImageRef* raw, const bool has_out )
 {
 	GPRoute R = gp_refuse;
-	const bool two_pass = (( p -> variant & AVIRHIP_VARIANT_UPG_TWO_PASS ) != 0 );
-	// (a forced variant bit 4 = "fused whatever the size": tests)
-	const bool fused = (( p -> variant & AVIRHIP_VARIANT_UPG_FUSED ) != 0 );
 
 	// Large upsizing plans of float RGBA sources run both passes in one launch
 	// (gfuse.hip): no intermediate image. "Large": a fused chunk repeats the
@@ -1521,11 +1629,8 @@ static GPRoute route_avir( const avirhip_plan* p, const GPData* D,
 	// crossing is at about 7 Mpixels of output.
 	// AVIRHIP_GF_MINPIX moves it (0: always), AVIRHIP_VARIANT_UPG_TWO_PASS
 	// keeps the two pass kernels (tests, A/B timing).
-	const bool use_gf = ( D -> h.a.mode == GP_PRE &&
-		D -> v.a.mode == GP_PRE && D -> h.a.nt == 12 && D -> v.a.nt == 12 &&
-		D -> h_geom && raw == nullptr && !two_pass &&
-		((long) p -> new_w * p -> new_h >= gf_minpix || fused ) &&
-		getenv( "AVIRHIP_NO_GFUSE" ) == nullptr );
+	// (gf_wanted; a half / bfloat16 source of such a call: io16_prefers_pack)
+	const bool use_gf = ( raw == nullptr && gf_wanted( p, D ));
 
 	if( use_gf )
 	{
@@ -1557,14 +1662,22 @@ static GPRoute route_avir( const avirhip_plan* p, const GPData* D,
 	const bool fsrc = ( raw != nullptr ? raw -> type == AVIRHIP_F32 : true );
 	static const bool opt_rgba = ( getenv( "AVIRHIP_SACC_OPT_RGBA" ) != nullptr &&
 		atoi( getenv( "AVIRHIP_SACC_OPT_RGBA" )) != 0 ); // (tuning aid)
-	const bool opt_wanted = ( raw != nullptr || opt_rgba ||
+	// A half / bfloat16 source read raw (gpass_takes_raw: its horizontal axis
+	// is k_gh's): a float source that can be non-finite -- never GPA_FINITE, no
+	// integer shortcut -- and none the accumulation kernels read, so it never
+	// runs optimistically either (`fsrc`). Its vertical pass reads the float
+	// RGBA rows of `mid` and is classified as the pack pass's float RGBA
+	// source is.
+	const bool h16 = ( raw != nullptr && dtype_is_float16_kind( raw -> type ));
+	const bool frgba = ( raw == nullptr || h16 );
+	const bool opt_wanted = (( raw != nullptr && !h16 ) || opt_rgba ||
 		( p -> variant & AVIRHIP_VARIANT_SACC_OPTIMISTIC ) != 0 );
 
-	// (raw == nullptr: float RGBA -- the exact kernels unless the variant asks)
-	const bool sa_always = ( int_src || ( raw == nullptr && !opt_wanted ));
-	// (raw == nullptr: a float RGBA source)
-	const bool use_sa_h = sa_wanted( D -> sa_h, sa_always, raw == nullptr );
-	const bool use_sa_v = sa_wanted( D -> sa_v, sa_always, raw == nullptr );
+	// (float RGBA -- the exact kernels unless the variant asks)
+	const bool sa_always = ( int_src || ( frgba && !opt_wanted ));
+	const bool use_sa_h = ( !h16 &&
+		sa_wanted( D -> sa_h, sa_always, raw == nullptr ));
+	const bool use_sa_v = sa_wanted( D -> sa_v, sa_always, frgba );
 
 	R.h = ( use_sa_h ? GPF_ACC : GPF_GATHER );
 	R.v = ( use_sa_v ? GPF_ACC : GPF_GATHER );
@@ -1587,18 +1700,16 @@ static GPRoute route_avir( const avirhip_plan* p, const GPData* D,
 	return( R );
 }
 
-// (both tuning aids are read by the first call of any plan)
+// (the tuning aid is read by the first call of any plan, as gf_minpix's is)
 static GPRoute gpass_route( const avirhip_plan* p, const GPData* D,
 	const float* dst, const ImageRef* raw, const bool has_out,
 	const LancirOut* lout )
 {
-	static const long gf_minpix = ( getenv( "AVIRHIP_GF_MINPIX" ) != nullptr ?
-		atol( getenv( "AVIRHIP_GF_MINPIX" )) : 7000000L );
 	static const double lf_ratio = ( getenv( "AVIRHIP_LF_INT_RATIO" ) != nullptr ?
 		atof( getenv( "AVIRHIP_LF_INT_RATIO" )) : -1.0 );
 
 	return( p -> is_lancir ? route_lancir( p, D, dst, raw, lout, lf_ratio ) :
-		route_avir( p, D, raw, has_out, gf_minpix ));
+		route_avir( p, D, raw, has_out ));
 }
 
 // ---- one function per outcome. What belongs to the call:
@@ -1894,18 +2005,29 @@ int gpass_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 
 	if( iout != nullptr )
 	{
+		// (half / bfloat16 pixels of 1-4 channels: narrowed in the store,
+		// gp_store_int_row; elements are stored whole, so the image is a
+		// multiple of their size)
+		const bool out16 = dtype_is_float16_kind( p -> out_type );
+
 		if( p -> is_lancir || p -> gamma ||
 			( p -> out_type != AVIRHIP_F32 &&
 			p -> dither != AVIRHIP_DITHER_DEF ) ||
 			( p -> out_type != AVIRHIP_U8 && p -> out_type != AVIRHIP_U16 &&
-			!( p -> out_type == AVIRHIP_F32 && p -> io_ch < 4 )) ||
+			!( p -> out_type == AVIRHIP_F32 && p -> io_ch < 4 ) && !out16 ) ||
 			( p -> out_type == AVIRHIP_U8 && p -> io_ch == 4 &&
-			(( (uintptr_t) iout & 3 ) != 0 )))
+			(( (uintptr_t) iout & 3 ) != 0 )) ||
+			( out16 && ( !gpass_io16() || ( (uintptr_t) iout & 1 ) != 0 )))
 		{
 			return( 1 );
 		}
 
 		gp_make_out( p, iout, O );
+
+		if( out16 )
+		{
+			O.fin = 0; // (no integer stage: none of its shortcuts)
+		}
 	}
 
 	GPData* D = (GPData*) p -> gpass;
@@ -1914,7 +2036,11 @@ int gpass_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 	if( D == nullptr || ( iout == nullptr && ( (uintptr_t) dst & 15 )) ||
 		( p -> is_lancir && ( p -> new_stride & 3 )) ||
 		( raw == nullptr && (( (uintptr_t) src & 15 ) || ( src_stride & 3 ))) ||
-		( raw != nullptr && !p -> is_lancir && !gpass_takes_raw( p )))
+		( raw != nullptr && !p -> is_lancir && !gpass_takes_raw( p )) ||
+		// (half / bfloat16 elements are loaded whole: run_h refuses fewer
+		// than four of them, as it does for every typed source)
+		( raw != nullptr && dtype_is_float16_kind( raw -> type ) &&
+		( (uintptr_t) raw -> ptr & 1 ) != 0 ))
 	{
 		return( 1 );
 	}

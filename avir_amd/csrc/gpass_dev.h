@@ -246,6 +246,63 @@ __device__ __forceinline__ void gp_store_int( const GPOut& O, const long row,
 	}
 }
 
+// Half / bfloat16 pixels of 1-4 channels (avirhip.h), for gp_store_int_row: the
+// float result narrowed to nearest even and nothing else -- no clamp, no PkOut
+// scale, no integer rounding, none of the `fin` shortcuts. Half: plain
+// conversions (v_cvt_f16_f32, denormals kept, beyond +-65504 +-Inf; never the
+// pkrtz form); bfloat16: one v_cvt_pk_bf16_f32 per channel pair. RGBA: one
+// 8-byte store per lane, 512 contiguous bytes per wave row.
+__device__ __forceinline__ void gp_store_f16_row( const GPOut& O,
+	const long row, const int x, const f4 o, const bool ok )
+{
+	unsigned int w0, w1;
+
+	if( O.type == AVIRHIP_F16 )
+	{
+		const float v0 = o.x, v1 = o.y, v2 = o.z, v3 = o.w;
+		const unsigned int h0 = __builtin_bit_cast( unsigned short,
+			(_Float16) v0 );
+		const unsigned int h1 = __builtin_bit_cast( unsigned short,
+			(_Float16) v1 );
+		const unsigned int h2 = __builtin_bit_cast( unsigned short,
+			(_Float16) v2 );
+		const unsigned int h3 = __builtin_bit_cast( unsigned short,
+			(_Float16) v3 );
+		w0 = h0 | ( h1 << 16 );
+		w1 = h2 | ( h3 << 16 );
+	}
+	else
+	{
+		typedef float gf2 __attribute__(( ext_vector_type( 2 )));
+		typedef __bf16 gbf2 __attribute__(( ext_vector_type( 2 )));
+		const gf2 lo = { o.x, o.y }, hi = { o.z, o.w };
+		w0 = __builtin_bit_cast( unsigned int,
+			__builtin_convertvector( lo, gbf2 ));
+		w1 = __builtin_bit_cast( unsigned int,
+			__builtin_convertvector( hi, gbf2 ));
+	}
+
+	if( ok )
+	{
+		unsigned short* const p = (unsigned short*) O.base +
+			row * O.stride + (long) x * O.ch;
+
+		if( O.ch == 4 )
+		{
+			typedef unsigned int u2u __attribute__(( ext_vector_type( 2 ),
+				aligned( 2 )));
+			u2u w; w.x = w0; w.y = w1;
+			*(u2u*) p = w;
+		}
+		else
+		{
+			p[ 0 ] = (unsigned short) w0;
+			if( O.ch > 1 ) p[ 1 ] = (unsigned short) ( w0 >> 16 );
+			if( O.ch > 2 ) p[ 2 ] = (unsigned short) w1;
+		}
+	}
+}
+
 // The same, called by EVERY lane of the wave (`ok`: this lane's pixel exists):
 // lanes are consecutive pixels x of one row. RGB uint8 pixels -- three byte
 // stores per lane in gp_store_int, three store instructions per output row and
@@ -260,6 +317,12 @@ __device__ __forceinline__ void gp_store_int_row( const GPOut& O, const long row
 {
 	if( !( O.type == AVIRHIP_U8 && O.ch == 3 ))
 	{
+		// (tested behind the RGB uint8 form, which keeps its order of tests)
+		if( O.type == AVIRHIP_F16 || O.type == AVIRHIP_BF16 )
+		{
+			gp_store_f16_row( O, row, x, o, ok );
+		}
+		else
 		if( ok )
 		{
 			gp_store_int( O, row, x, o );
@@ -862,7 +925,8 @@ __device__ __forceinline__ T gp_dot( const int nt_, LD ld, CF cf4,
 	return( acc );
 }
 
-// One raw pixel (1 uint8, 2 uint16, 3 float elements; `ch` of them) as float
+// One raw pixel (1 uint8, 2 uint16, 3 float, 4 half, 5 bfloat16 elements; `ch`
+// of them) as float
 // RGBA with zero padding: ONE load of four elements at the pixel's (possibly
 // unaligned) address -- what it reads past the pixel is dropped; only where
 // those four elements would cross the end of the image (its last pixel) are
@@ -902,6 +966,45 @@ __device__ __forceinline__ f4 gp_load_raw( const void* const base,
 		{
 			v[ c ] = ( c < ch ? (float) (unsigned int) (( w >> ( 16 * c )) &
 				0xffffull ) : 0.0f );
+		}
+	}
+	else
+	if( kind == 4 || kind == 5 )
+	{
+		// half / bfloat16 elements: the same 8-byte load and last-pixel shift
+		// as kind 2, widened exactly for every bit pattern -- what the pack
+		// pass writes (generic.hip: k_pack)
+		typedef unsigned long long u64u __attribute__(( aligned( 2 )));
+		const unsigned long long w = *(const u64u*) (
+			(const unsigned short*) base + ea ) >> ( 16 * sh );
+		const unsigned int lo = (unsigned int) w;
+		const unsigned int hi = (unsigned int) ( w >> 32 );
+		float ww[ 4 ];
+
+		if( kind == 4 )
+		{
+			// (v_cvt_f32_f16: half denormals kept)
+			ww[ 0 ] = (float) __builtin_bit_cast( _Float16,
+				(unsigned short) ( lo & 0xffffu ));
+			ww[ 1 ] = (float) __builtin_bit_cast( _Float16,
+				(unsigned short) ( lo >> 16 ));
+			ww[ 2 ] = (float) __builtin_bit_cast( _Float16,
+				(unsigned short) ( hi & 0xffffu ));
+			ww[ 3 ] = (float) __builtin_bit_cast( _Float16,
+				(unsigned short) ( hi >> 16 ));
+		}
+		else
+		{
+			// (bits << 16: a shift and a mask per dword)
+			ww[ 0 ] = __uint_as_float( lo << 16 );
+			ww[ 1 ] = __uint_as_float( lo & 0xffff0000u );
+			ww[ 2 ] = __uint_as_float( hi << 16 );
+			ww[ 3 ] = __uint_as_float( hi & 0xffff0000u );
+		}
+#pragma unroll
+		for( int c = 0; c < 4; c++ )
+		{
+			v[ c ] = ( c < ch ? ww[ c ] : 0.0f );
 		}
 	}
 	else

@@ -465,6 +465,11 @@ void gpass_release( avirhip_plan* p );
 bool gpass_ok( const avirhip_plan* p );
 bool gpass_preferred( const avirhip_plan* p );
 bool gpass_takes_raw( const avirhip_plan* p );
+// whether the pass kernels read and store half / bfloat16 pixels themselves
+// (AVIRHIP_GP_NO_IO16, read per call: the pack pass and the output stage)
+bool gpass_io16();
+// the last source row the first pass of output rows [row0, row1) reads
+int gpass_last_src_row( const avirhip_plan* p, int row0, int row1 );
 bool gpass_lancir_takes_raw( const avirhip_plan* p, const ImageRef& raw );
 // `raw`: the image the first pass reads instead of `src`; `iout`: the last pass
 // of an AVIR plan stores the caller's pixels there; `lout`: the last pass of a

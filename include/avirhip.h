@@ -69,8 +69,12 @@ typedef enum avirhip_dtype {
  * (Three kernels read and store half RGBA pixels themselves, one launch over
  * the caller's images: CImageResizer's exact-2x marching kernel k_up2, its
  * whole-ratio (2x, 3x) downsizing kernel k_dnfh, and CLancIR's exact-2x kernel
- * k_lanc2h; everywhere else the pack pass widens and the output stage
- * narrows.) */
+ * k_lanc2h. At any other ratio CImageResizer's pass kernels do, for pixels of
+ * 1-4 channels: k_gh reads a half source where it lies, and the last pass
+ * -- k_gv, k_gf, the accumulation kernels k_sacc* -- narrows and stores a half
+ * result; an axis that streams (k >= 2), k_gf and k_gh2 read the pack pass's
+ * float copy of the source. Everywhere else -- the tiles, gamma, CLancIR's
+ * other ratios -- the pack pass widens and the output stage narrows.) */
 	AVIRHIP_F16 = 5,
 	/* bfloat16 elements: 16 bits holding the upper half of an IEEE binary32.
 	 * A call with bfloat16 elements is DEFINED by the same call with float
@@ -90,7 +94,8 @@ typedef enum avirhip_dtype {
 	 * refuse bfloat16 elements (AVIRHIP_EUNSUPPORTED) as they refuse half ones;
 	 * CLancIR accepts them on either side under the same rule. (k_up2, k_dnfh
  * and k_lanc2h read and store bfloat16 RGBA pixels themselves, as they do
- * half ones.) */
+ * half ones, and so do the pass kernels -- k_gh the source, k_gv / k_gf /
+ * k_sacc* the result, 1-4 channels -- at every other ratio.) */
 	AVIRHIP_BF16 = 6
 } avirhip_dtype;
 
@@ -316,7 +321,13 @@ int avirhip_plan_get_path(const avirhip_plan* plan);
 #define AVIRHIP_VARIANT_UPG_TWO_PASS 8
 /* ... and the fused launch whatever the frame size (automatically: frames of
  * 7 Mpixels of output and more; CLancIR plans with integer results: up to
- * about 3x horizontally) */
+ * about 3x horizontally). (The fused kernel k_gf reads float RGBA rows only:
+ * a half / bfloat16 source has the pack pass in front of it, a half / bfloat16
+ * result is narrowed and stored by it. With AVIRHIP_VARIANT_UPG_TWO_PASS k_gh
+ * reads such a source where it lies. The environment variable
+ * AVIRHIP_GP_NO_IO16, read per call, puts the pack pass and the output stage
+ * around the pass kernels for every half / bfloat16 image: A/B timing and
+ * differential tests.) */
 #define AVIRHIP_VARIANT_UPG_FUSED 16
 /* float RGBA sources on downsizing axes: the branch-free accumulation kernels
  * run optimistically (exact kernels behind an alarm) as they do for float

@@ -30,9 +30,19 @@ library's md5 and the device clocks.
       (AVIRHIP_VARIANT_DN_UNFUSED_IO: the road before k_dnfh),
   (d) bfloat16 -> bfloat16 fused, (e) the same unfused,
   (f) float32 -> half, (g) half -> float32.
+--gpass measures general ratios on the pass kernels (path 5, the automatic
+path of every shape it runs) by the same method -- 1920x1080 -> 2500x1400,
+3840x2160 -> 2560x1440 and -> 2000x1125, 1920x1080 -> 5760x3240, 3840x2160 ->
+6144x3456, 5184x3456 -> 1920x1280 -- as float32, the 16-bit call as it runs
+automatically, the same call under AVIRHIP_GP_NO_IO16 (pack pass and output
+stage: the road before the typed k_gh and the narrowing store), and the typed
+k_gh forced where k_gf / k_gh2 keep the pack pass; with PARENT.so also RGB
+uint8 on both builds (the store function the integer stage shares).
 
-usage: python tools/half_timing.py [--bf16 | --lancir | --dnf] [PARENT.so]
-       [REPS=5]"""
+usage: python tools/half_timing.py [--bf16 | --lancir | --dnf | --gpass]
+       [PARENT.so] [REPS=5] [ONLY]
+(ONLY, with --gpass: the shapes whose names hold one of these comma-separated
+words, e.g. "u8")"""
 import ctypes as C
 import hashlib
 import os
@@ -243,7 +253,157 @@ def dnf_main(argv):
         torch.cuda.empty_cache()
 
 
+class _env(object):
+    """`with _env(d):` -- the variables of a call (read per call by the
+    library), put back after."""
+
+    def __init__(self, env):
+        self.env = env
+
+    def __enter__(self):
+        self.keep = {k: os.environ.get(k) for k in self.env}
+        os.environ.update(self.env)
+
+    def __exit__(self, *a):
+        for k, v in self.keep.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+        return False
+
+
+def gpass_main(argv):
+    """--gpass: general ratios on the automatic path (the pass kernels, path 5,
+    at every shape below). Rows per shape and type: float32; the 16-bit call
+    as it runs automatically; the same call under AVIRHIP_GP_NO_IO16 (the road
+    before the typed k_gh and the narrowing store: pack pass, kernels, output
+    stage -- the baseline); and, where the float RGBA kernel of the shape has
+    no typed form (k_gf, k_gh2), the typed k_gh road forced
+    (AVIRHIP_GP_IO16_GF / AVIRHIP_GP_IO16_GH2 = 1).
+    With PARENT.so: RGB uint8 through the shared store function, both builds
+    alternating (cfg1 640x480 -> 1024x768, 1920x1080 -> 2500x1400)."""
+    import numpy as np
+    import torch
+    import avir_amd
+    from avir_amd import abi, synth
+    parent = argv[1] if len(argv) > 1 and argv[1] != "-" else None
+    reps = int(argv[2]) if len(argv) > 2 else 5
+    lib = abi.load()
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    header(lib, parent)
+    TD = {abi.F32: torch.float32, abi.F16: torch.float16,
+          abi.BF16: torch.bfloat16, abi.U8: torch.uint8}
+    ES = {abi.F32: 4, abi.F16: 2, abi.BF16: 2, abi.U8: 1}
+    NO = {"AVIRHIP_GP_NO_IO16": "1"}
+    GF = {"AVIRHIP_GP_IO16_GF": "1"}
+    GH2 = {"AVIRHIP_GP_IO16_GH2": "1"}
+    F32, F16, BF16, U8 = abi.F32, abi.F16, abi.BF16, abi.U8
+
+    def same16(tag, ti, to, ch=4, alt=None, altname=""):
+        rows = [("%s fused (automatic)" % tag, lib, ti, to, ch, {}),
+                ("%s pack + output stage" % tag, lib, ti, to, ch, NO)]
+        if alt is not None:
+            rows.append(("%s %s" % (tag, altname), lib, ti, to, ch, alt))
+        return rows
+
+    shapes = [
+        ("1080p x1.3", (1920, 1080, 2500, 1400),
+         same16("f16->f16", F16, F16) + same16("bf16->bf16", BF16, BF16) +
+         same16("f32->bf16", F32, BF16) + same16("RGB f16->f16", F16, F16, 3)),
+        ("4K k1.5", (3840, 2160, 2560, 1440),
+         same16("f16->f16", F16, F16) + same16("bf16->bf16", BF16, BF16) +
+         same16("f32->bf16", F32, BF16)),
+        ("4K k1.92", (3840, 2160, 2000, 1125),
+         same16("f16->f16", F16, F16, 4, GH2, "typed k_gh forced") +
+         same16("bf16->bf16", BF16, BF16, 4, GH2, "typed k_gh forced")),
+        ("1080p x3", (1920, 1080, 5760, 3240),
+         same16("f16->f16", F16, F16, 4, GF, "typed k_gh + k_gv forced") +
+         same16("bf16->bf16", BF16, BF16, 4, GF, "typed k_gh + k_gv forced")),
+        ("4K x1.6", (3840, 2160, 6144, 3456),
+         same16("f16->f16", F16, F16, 4, GF, "typed k_gh + k_gv forced")),
+        ("5184 k2.7", (5184, 3456, 1920, 1280),
+         same16("f16->f16", F16, F16) + same16("bf16->bf16", BF16, BF16)),
+    ]
+    if parent:
+        P = abi.load_path(parent)
+        for name, g in (("cfg1 RGB u8", (640, 480, 1024, 768)),
+                        ("1080p x1.3 RGB u8", (1920, 1080, 2500, 1400))):
+            shapes.append((name, g, [("u8->u8 this build", lib, U8, U8, 3, {}),
+                                     ("u8->u8 parent build", P, U8, U8, 3, {}),
+                                     ("u8->u8 this build again", lib, U8, U8, 3,
+                                      {})]))
+    only = argv[3].split(",") if len(argv) > 3 else None  # (--gpass: ONLY)
+    for name, (sw, sh, nw, nh), rows in shapes:
+        if only is not None and not any(o in name for o in only):
+            continue
+        base = synth.lcg_f32((sh, sw, 4))
+        if not name.endswith("u8"):
+            rows = [("f32->f32", lib, F32, F32, 4, {})] + rows
+        run, keep, first = {}, [], {}
+        for tag, L, ti, to, ch, env in rows:
+            pair = sw * sh * ch * ES[ti] + nw * nh * ch * ES[to]
+            n = max(2, -(-(512 << 20) // pair))
+            ring = []
+            for i in range(n):
+                b = np.roll(base, i, axis=0)[:, :, :ch]
+                if ti == U8:
+                    b = b * 255.0
+                s = torch.from_numpy(np.ascontiguousarray(b)).to(dev).to(TD[ti])
+                d = torch.empty((nh, nw, ch), dtype=TD[to], device=dev)
+                ring.append((s, d))
+            with abi.using(L):
+                r = avir_amd.CImageResizer(8 if to == U8 else 16)
+                p = r.plan(sw, sh, nw, nh, ch, 0.0, None, ti, to)
+            keep.append((r, ring))
+
+            def once(L=L, p=p, ring=ring, env=env):
+                t = 0.0
+                ms = C.c_double()
+                with _env(env):
+                    for s, d in ring:
+                        abi.check(L.avirhip_time_resize(
+                            p, s.data_ptr(), d.data_ptr(), 1, st, C.byref(ms)),
+                            "time_resize")
+                        t += ms.value
+                return t / len(ring)
+            run[tag] = (once, pair, n, L, p)
+            first[tag] = ring[0][1]
+        for tag in run:  # warm-up, clocks
+            for _ in range(10):
+                run[tag][0]()
+        torch.cuda.synchronize()
+        res = {tag: [] for tag in run}
+        loops = 20
+        for _ in range(reps):
+            for tag in run:
+                res[tag].append(sum(run[tag][0]() for _ in range(loops)) / loops)
+        print("%s (%dx%d -> %dx%d), path %d, %d reps x %d ring passes:" % (
+            name, sw, sh, nw, nh, lib.avirhip_plan_get_path(run[rows[-1][0]][4]),
+            reps, loops))
+        for tag in run:
+            v = sorted(res[tag])
+            med = v[len(v) // 2]
+            print("  %-44s %.4f ms  (min %.4f max %.4f)  %6.1f MB/call  "
+                  "ring %d  plan holds %.1f MB" % (
+                      tag, med, v[0], v[-1], run[tag][1] / 1e6, run[tag][2],
+                      run[tag][3].avirhip_plan_device_bytes(run[tag][4]) / 1e6),
+                  flush=True)
+        tags = [t for t in run if t != "f32->f32"]
+        for i in range(0, len(tags) - 1):
+            a, b = tags[i], tags[i + 1]
+            if a.split(" fused")[0] == b.split(" pack")[0] or "u8" in a:
+                print("  %s / %s bit-identical: %s" % (a, b, torch.equal(
+                    first[a].view(torch.uint8), first[b].view(torch.uint8))),
+                    flush=True)
+        del keep, run, first
+        torch.cuda.empty_cache()
+
+
 def main():
+    if "--gpass" in sys.argv:
+        return gpass_main([a for a in sys.argv if a != "--gpass"])
     if "--lancir" in sys.argv:
         return lancir_main([a for a in sys.argv if a != "--lancir"])
     if "--dnf" in sys.argv:
