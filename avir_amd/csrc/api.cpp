@@ -918,11 +918,29 @@ static int lancir_owner( avirhip_plan* p, const void* src, void* dst,
 		return( AVIRHIP_OK );
 	}
 
-	// (double and uint32 elements, lancir.h:373-377, half and bfloat16 ones: the
-	// pack pass and the output stage convert them; the fast kernels' own
-	// loaders and fused stores know uint8, uint16 and float)
-	const bool in_fast = ( p -> in_type <= AVIRHIP_F32 );
-	const bool out_fast = ( p -> out_type <= AVIRHIP_F32 );
+	// (double and uint32 elements, lancir.h:373-377: the pack pass and the
+	// output stage convert them; the fast kernels' own loaders and fused stores
+	// know uint8, uint16 and float)
+	// Half and bfloat16 elements: the pass kernels alone know them (path 5:
+	// k_lf's and k_gv's raw loaders, kinds 4 / 5; gp_store_lancir_row< 3 > of
+	// k_lf and k_gh) -- k_lanc2's loader and fused store do not, so an inner
+	// plan on path 4 keeps the pack pass and the output stage around it, also
+	// where it falls through to the pass kernels by itself, and every exact-2x
+	// plan (q -> lanc2: RGB, RGBA) stays on the roads it had (k_lanc2h below;
+	// RGB and integer results behind a 16-bit source: pack pass and output
+	// stage), also when path 5 is forced on it. Each
+	// side is decided here, once, on its own: the source by the loaders'
+	// predicates below, the result by its base address -- elements are stored
+	// whole, so an odd base goes through the float result and the output
+	// stage. AVIRHIP_GP_NO_IO16 (read per call), as for CImageResizer's pass
+	// kernels: both stages for every 16-bit image.
+	const bool h_in = dtype_is_float16_kind( p -> in_type );
+	const bool h_out = dtype_is_float16_kind( p -> out_type );
+	const int qpath = ( q -> path != 0 ? q -> path : q -> auto_path );
+	const bool io16 = ( qpath == 5 && q -> lanc2 == nullptr && gpass_io16() );
+	const bool in_fast = ( p -> in_type <= AVIRHIP_F32 || ( h_in && io16 ));
+	const bool out_fast = ( p -> out_type <= AVIRHIP_F32 || ( h_out && io16 &&
+		( (uintptr_t) dst & 1 ) == 0 ));
 	const ImageRef img = { src, p -> in_type, p -> io_ch, p -> src_stride };
 	const LancirOut ostage = { dst, p -> new_stride, p -> out_type, p -> io_ch,
 		p -> l_unity, p -> l_out_mul, p -> l_clamp };
@@ -944,7 +962,7 @@ static int lancir_owner( avirhip_plan* p, const void* src, void* dst,
 	// otherwise the pack pass makes its float RGBA copy
 	const ImageRef* raw = ( fio && in_fast &&
 		( gpass_lancir_takes_raw( q, img ) ||
-		( lanc2_takes_raw( q, img ) && dst2 )) ? &img : nullptr );
+		( !h_in && lanc2_takes_raw( q, img ) && dst2 )) ? &img : nullptr );
 	const LancirOut* const lout = ( fio && out_fast ? &ostage : nullptr );
 
 	auto pack = [&]() -> int
@@ -971,9 +989,10 @@ static int lancir_owner( avirhip_plan* p, const void* src, void* dst,
 	};
 
 	// Exact 2x RGBA with a half / bfloat16 image on either side (lanc2h.hip):
-	// one launch, on the automatic path whatever the frame's size (the pass
-	// kernels know neither type: behind them the pack pass and the output
-	// stage would run) and on forced path 4. A half / bfloat16 RESULT is
+	// one launch, on the automatic path whatever the frame's size (at exact 2x
+	// the pass kernels are not offered either type -- `io16` above: behind them
+	// the pack pass and the output stage would run) and on forced path 4. A
+	// half / bfloat16 RESULT is
 	// narrowed and stored by the kernel, whatever the source: the kernel reads
 	// a half / bfloat16 / float RGBA source where it lies, the pack pass's
 	// float copy of any other. A half / bfloat16 SOURCE with a float result is
@@ -982,9 +1001,6 @@ static int lancir_owner( avirhip_plan* p, const void* src, void* dst,
 	// k_lanc2's fused store behind the pack pass, below. An image that
 	// lanc2h_image_ok refuses goes through its float copy, and a call left
 	// with float on both sides takes the general road below.
-	const bool h_in = dtype_is_float16_kind( p -> in_type );
-	const bool h_out = dtype_is_float16_kind( p -> out_type );
-
 	if( fio && ( h_out || ( h_in && p -> out_type == AVIRHIP_F32 )) &&
 		p -> io_ch == 4 && q -> l_order == 4 && q -> lanc2 != nullptr &&
 		( p -> path == 0 || p -> path == 4 ))

@@ -1184,7 +1184,8 @@ static void launch_gh2( const GHParams& P, int items, size_t lds,
 
 // src_kind: 0 float RGBA (LDS-DMA); 1 uint8, 2 uint16, 3 float, 4 half,
 // 5 bfloat16 pixels read raw
-// (LANCIR plans: 1 / 2 = the output stage stores uint8 RGB / RGBA pixels)
+// (LANCIR plans: 1 / 2 = the output stage stores uint8 RGB / RGBA pixels, 3 =
+// half / bfloat16 pixels of 1-4 channels: gp_store_lancir_row's kinds)
 template< int MODE, bool LANC >
 static void launch_gh( const GHParams& P, int src_kind, int items, size_t lds,
 	hipStream_t st )
@@ -1193,8 +1194,7 @@ static void launch_gh( const GHParams& P, int src_kind, int items, size_t lds,
 	{
 		case 1: launch_gh2< MODE, LANC, 1 >( P, items, lds, st ); break;
 		case 2: launch_gh2< MODE, LANC, 2 >( P, items, lds, st ); break;
-		case 3: launch_gh2< MODE, LANC, ( LANC ? 0 : 3 ) >( P, items, lds, st );
-			break;
+		case 3: launch_gh2< MODE, LANC, 3 >( P, items, lds, st ); break;
 		case 4: launch_gh2< MODE, LANC, ( LANC ? 0 : 4 ) >( P, items, lds, st );
 			break;
 		case 5: launch_gh2< MODE, LANC, ( LANC ? 0 : 5 ) >( P, items, lds, st );
@@ -1346,7 +1346,17 @@ static int run_h( const GPData* D, const GPPass& G, hipStream_t st )
 
 	if( A.lanc )
 	{
-		launch_gh< GP_NONE, true >( P, ( P.lout.on != 0 &&
+		const bool out16 = ( P.lout.on != 0 &&
+			dtype_is_float16_kind( P.lout.type ));
+
+		// (the store's kind 0 knows uint8, uint16 and float elements)
+		if( P.lout.on != 0 && !out16 && P.lout.type != AVIRHIP_U8 &&
+			P.lout.type != AVIRHIP_U16 && P.lout.type != AVIRHIP_F32 )
+		{
+			return( 1 );
+		}
+
+		launch_gh< GP_NONE, true >( P, ( out16 ? 3 : P.lout.on != 0 &&
 			P.lout.type == AVIRHIP_U8 && P.lout.ch >= 3 ? P.lout.ch - 2 : 0 ),
 			items, lds, st );
 	}
@@ -1412,7 +1422,11 @@ int gpass_last_src_row( const avirhip_plan* p, int row0, int row1 )
 
 // LANCIR (an inner plan): whether its vertical pass -- the first one -- reads
 // the owner's integer / narrower image as it is (whole-pixel lanes of the
-// register-window variants of k_gv: gpass_v_raw_ok).
+// register-window variants of k_gv: gpass_v_raw_ok, which names the element
+// types the loaders know -- uint8, uint16, float, half, bfloat16; k_lf's own
+// test, lfuse_takes_raw, asks the same of base and pitch). The owner offers a
+// half / bfloat16 image only on this path and not under AVIRHIP_GP_NO_IO16
+// (lancir_owner).
 bool gpass_lancir_takes_raw( const avirhip_plan* p, const ImageRef& img )
 {
 	const GPData* D = (const GPData*) p -> gpass;
@@ -1597,7 +1611,16 @@ static GPRoute route_lancir( const avirhip_plan* p, const GPData* D,
 	// 0.086, x4 0.166 / 0.136; RGBA uint8 x3 0.086 / 0.088, x4 0.152 / 0.140;
 	// float results: fused wins at every ratio, x3 0.082 / 0.126;
 	// profiles/r05_lanc, tools/rounds/r05_lf2.sh; lf_ratio >= 0 replaces both)
+	// Half / bfloat16 results (2 bytes per element, gp_store_lancir_row< 3 >):
+	// the float rule, fused at every ratio -- 1920x1080 half RGBA in and out,
+	// one process, a ring of buffers, k_lf / k_gv + k_gh: x1.5 0.033 / 0.042 ms,
+	// x2.5 0.068 / 0.083, x3 0.095 / 0.106, x4 0.162 / 0.164 (tools/
+	// half_timing.py --lancgp, NOTEBOOK 27; spread about 0.001, so x4 is a
+	// tie). The store has no clamps, roundings or tail rule
+	// to run per strip, and the two passes' `mid` costs what it costs a float
+	// result; AVIRHIP_LF_INT_RATIO does not move this class.
 	const bool lf_pays = ( lout == nullptr || lout -> type == AVIRHIP_F32 ||
+		dtype_is_float16_kind( lout -> type ) ||
 		(double) p -> new_w <= (double) p -> src_w * ( lf_ratio >= 0.0 ?
 		lf_ratio : ( lout -> ch == 4 ? 3.2 : 2.7 )) || fused );
 	const bool use_lf = ( D -> lf_ow != 0 && lf_pays && ( raw == nullptr ||
@@ -1744,7 +1767,9 @@ static int run_lanc_fused( const avirhip_plan* p, const GPData* D,
 		const int esz = (int) dtype_size( C.raw -> type );
 
 		G.raw = C.raw -> ptr; G.raw_ss = C.raw -> stride;
-		G.raw_kind = ( esz == 1 ? 1 : ( esz == 2 ? 2 : 3 ));
+		// (half / bfloat16 pixels: uint16's geometry -- the same bytes per
+		// pixel, instruction count and range -- and a conversion of their own)
+		G.raw_kind = gp_raw_kind( C.raw -> type );
 		G.raw_ch = C.raw -> ch; G.raw_bpp = esz * C.raw -> ch;
 		G.raw_bytes = image_dma_bytes( *C.raw, p -> src_h, p -> src_w );
 		G.raw_tdn = ( 64 * G.raw_bpp + ( G.raw_bpp & 3 ? 3 : 0 ) + 255 ) >> 8;

@@ -403,7 +403,8 @@ __device__ __forceinline__ void gp_store_int_row( const GPOut& O, const long row
 struct GPLOut
 {
 	int on;
-	int type;        // AVIRHIP_U8 / AVIRHIP_U16 / AVIRHIP_F32
+	int type;        // AVIRHIP_U8 / AVIRHIP_U16 / AVIRHIP_F32 / AVIRHIP_F16 /
+	                 // AVIRHIP_BF16 (the last two: gp_store_lancir_row< 3 >)
 	int ch;          // channels of the caller's pixels (1..4)
 	int unity;
 	float out_mul, clampv;
@@ -462,6 +463,74 @@ __device__ __forceinline__ void gp_store_lancir( const GPLOut& O,
 	}
 }
 
+// Half / bfloat16 results (GPLOut.type AVIRHIP_F16 / AVIRHIP_BF16, 1-4
+// channels), for gp_store_lancir_row< 3 >: the gain exactly as the float branch
+// above applies it (v * out_mul unless unity), then the float narrowed to
+// nearest even and nothing else -- no clamp, no integer rounding, no tail rule
+// (outputScanline's float form, lancir.h:1786-1856; what k_lancir_out /
+// k_lancir_out_pad do behind the float result). Half: plain conversions
+// (v_cvt_f16_f32, denormals kept, beyond +-65504 +-Inf; never the pkrtz form);
+// bfloat16: v_cvt_pk_bf16_f32, the header's integer formula, NaN stays NaN.
+// RGBA: one 8-byte store per lane (any 2-byte-aligned address: 512 contiguous
+// bytes per wave row); 1-3 channels: element stores. The host offers this store
+// only for an even base address (lancir_owner).
+__device__ __forceinline__ void gp_store_lancir_f16( const GPLOut& O,
+	const long row, const int x, const f4 o, const bool ok )
+{
+	float v0 = o.x, v1 = o.y, v2 = o.z, v3 = o.w;
+	unsigned int w0, w1;
+
+	if( !O.unity )
+	{
+		v0 = v0 * O.out_mul; v1 = v1 * O.out_mul;
+		v2 = v2 * O.out_mul; v3 = v3 * O.out_mul;
+	}
+
+	if( O.type == AVIRHIP_F16 )
+	{
+		const unsigned int h0 = __builtin_bit_cast( unsigned short,
+			(_Float16) v0 );
+		const unsigned int h1 = __builtin_bit_cast( unsigned short,
+			(_Float16) v1 );
+		const unsigned int h2 = __builtin_bit_cast( unsigned short,
+			(_Float16) v2 );
+		const unsigned int h3 = __builtin_bit_cast( unsigned short,
+			(_Float16) v3 );
+		w0 = h0 | ( h1 << 16 );
+		w1 = h2 | ( h3 << 16 );
+	}
+	else
+	{
+		typedef float gf2 __attribute__(( ext_vector_type( 2 )));
+		typedef __bf16 gbf2 __attribute__(( ext_vector_type( 2 )));
+		const gf2 lo = { v0, v1 }, hi = { v2, v3 };
+		w0 = __builtin_bit_cast( unsigned int,
+			__builtin_convertvector( lo, gbf2 ));
+		w1 = __builtin_bit_cast( unsigned int,
+			__builtin_convertvector( hi, gbf2 ));
+	}
+
+	if( ok )
+	{
+		unsigned short* const p = (unsigned short*) O.base +
+			row * O.stride + (long) x * O.ch;
+
+		if( O.ch == 4 )
+		{
+			typedef unsigned int u2u __attribute__(( ext_vector_type( 2 ),
+				aligned( 2 )));
+			u2u w; w.x = w0; w.y = w1;
+			*(u2u*) p = w;
+		}
+		else
+		{
+			p[ 0 ] = (unsigned short) w0;
+			if( O.ch > 1 ) p[ 1 ] = (unsigned short) ( w0 >> 16 );
+			if( O.ch > 2 ) p[ 2 ] = (unsigned short) w1;
+		}
+	}
+}
+
 // The same, called by EVERY lane of the wave (`ok`: this lane's pixel exists;
 // lanes are consecutive pixels x of one row). uint8 pixels of 3 or 4 channels
 // leave as whole dwords -- RGBA: the lane's own four bytes; RGB: a quad of lanes
@@ -473,11 +542,21 @@ __device__ __forceinline__ void gp_store_lancir( const GPLOut& O,
 // whose pixels reaches it (one ballot) rounds to nearest-even in straight-line
 // code; the first form branched per element and channel -- 25 branches per
 // output row, more cycles than the two dot products before them.
-// KIND: 0 = whatever O says; 1 / 2 = uint8 RGB / RGBA known at compile time.
+// KIND: 0 = whatever O says of uint8, uint16 and float elements; 1 / 2 = uint8
+// RGB / RGBA known at compile time; 3 = half / bfloat16 elements (O.type says
+// which; gp_store_lancir_f16) -- a kind of its own and not two more cases of
+// kind 0, whose variants thereby stay instruction for instruction what they
+// were (the launchers pick 3 for these two types and nothing else does).
 template< int KIND >
 __device__ __forceinline__ void gp_store_lancir_row( const GPLOut& O,
 	const long row, const int x, const f4 o, const bool ok )
 {
+	if constexpr( KIND == 3 )
+	{
+		gp_store_lancir_f16( O, row, x, o, ok );
+		return;
+	}
+
 	const int type = ( KIND != 0 ? AVIRHIP_U8 : O.type );
 	const int ch = ( KIND == 1 ? 3 : ( KIND == 2 ? 4 : O.ch ));
 	const bool b8 = ( type == AVIRHIP_U8 && ch >= 3 );
@@ -695,6 +774,35 @@ struct LFParams
 };
 
 int lfuse_launch( LFParams& P, hipStream_t st );
+// ... its variants for half / bfloat16 images (lfuse.hip, behind lfuse_launch)
+int lfuse_launch16( const LFParams& P, dim3 grid, size_t lds, hipStream_t st );
+
+// whether a k_lf call has a 16-bit float image on a side: a half / bfloat16
+// source read raw (raw_kind 4 / 5), or a half / bfloat16 result
+inline bool lf_is16( const LFParams& P )
+{
+	return(( P.raw != nullptr && P.raw_kind >= 4 ) || ( P.lout.on != 0 &&
+		( P.lout.type == AVIRHIP_F16 || P.lout.type == AVIRHIP_BF16 )));
+}
+
+// Element `c` of the 16-bit elements at `rp` (a row buffer in LDS) as float.
+// F16K false: a uint16 element, cast. F16K true: a half (`kind` 4:
+// v_cvt_f32_f16, denormals kept) or bfloat16 (5: bits << 16) element, widened
+// exactly for every bit pattern -- the pack pass's conversion (generic.hip).
+template< bool F16K >
+__device__ __forceinline__ float gp_elem16( const char* const rp, const int c,
+	const int kind )
+{
+	const unsigned short e = ((const unsigned short*) rp )[ c ];
+
+	if( !F16K )
+	{
+		return( (float) e );
+	}
+
+	return( kind == 4 ? (float) __builtin_bit_cast( _Float16, e ) :
+		__uint_as_float( (unsigned int) e << 16 ));
+}
 // gpass_h2.hip: k_gh2 (two gather outputs per lane); 1: no variant for the tap count
 int launch_gh2( const GHParams& P, int items, size_t lds, hipStream_t st );
 // (`img`: rows of `width` pixels, `in_len_v` of them)

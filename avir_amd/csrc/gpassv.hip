@@ -50,7 +50,10 @@ bool gpass_v_raw_ok( const GPAxis& A, const int v_rs, const int v_rc,
 		( (uintptr_t) img.ptr & 3 ) == 0 && (( img.stride * esz ) & 3 ) == 0 &&
 		image_dma_bytes( img, A.in_len, width ) != 0 &&
 		A.lanc && A.nt >= 6 && A.nt <= 24 && ( A.nt & 1 ) == 0 &&
-		gv_whole_px_fits( v_rs, v_rc ));
+		gv_whole_px_fits( v_rs, v_rc ) &&
+		// ... and an element type raw_px knows (uint8, uint16, float, half,
+		// bfloat16)
+		gp_raw_kind( img.type ) != 0 );
 }
 
 int gpass_run_v( const GPAxis& A_, int v_blk, int v_rs, int v_rc,
@@ -73,8 +76,8 @@ int gpass_run_v( const GPAxis& A_, int v_blk, int v_rs, int v_rc,
 		}
 
 		P.raw = raw -> ptr; P.raw_ss = raw -> stride; P.raw_ch = raw -> ch;
-		P.raw_kind = ( raw -> type == AVIRHIP_U8 ? 1 :
-			( raw -> type == AVIRHIP_U16 ? 2 : 3 ));
+		// (half / bfloat16: uint16's element size in `trow_b` and raw_dma)
+		P.raw_kind = gp_raw_kind( raw -> type );
 		// (rows are `stride` elements apart; the last one ends with its pixels)
 		P.raw_elems = (long) ( A_.in_len - 1 ) * raw -> stride +
 			(long) width * raw -> ch;

@@ -46,7 +46,11 @@ template<> struct GVLane< 2 > { typedef f4 T; };
 // LVAR (LANCIR variants only -- compiled in, they cost the float RGBA kernels
 // 35 .. 50 registers): bit 0 = the four-lane summation orders of 1-3 channel
 // images (gp_dot), bit 1 = the raw-source loader, bit 2 = ... of uint8 pixels
-// (the element type known at compile time: no dispatch in the step).
+// (the element type known at compile time: no dispatch in the step), bit 3 =
+// ... of half / bfloat16 pixels (P.raw_kind 4 / 5: uint16's geometry, the pack
+// pass's exact widening; gpassv_lancraw16.hip -- variants of their own, so that
+// the step of the uint16 / float ones, which the scalar unit binds, stays the
+// code it was).
 template< int MODE, bool LANC, int NTC, int RW, int WP, int LVAR >
 __global__ void __launch_bounds__( 64 ) k_gv( const GVParams P )
 {
@@ -394,10 +398,11 @@ __global__ void __launch_bounds__( 64 ) k_gv( const GVParams P )
 	constexpr bool TD = ( WP == 2 && ( LVAR & 2 ) != 0 );
 	const int tbpp = P.raw_dma;
 	const int raw_kind = (( LVAR & 4 ) ? 1 : P.raw_kind );
+	constexpr bool F16K = (( LVAR & 8 ) != 0 );
 	const __amdgpu_buffer_rsrc_t rraw = __builtin_amdgcn_make_buffer_rsrc(
 		(void*) P.raw, 0, P.raw_bytes, 0x00020000 );
-	const int trow_b = (int) P.raw_ss * ( raw_kind == 1 ? 1 :
-		( raw_kind == 2 ? 2 : 4 ));
+	const int trow_b = (int) P.raw_ss * ( F16K ? 2 : ( raw_kind == 1 ? 1 :
+		( raw_kind == 2 ? 2 : 4 )));
 	const bool tlane = ( lane < 4 * tbpp );
 
 	auto issue_raw = [&]( const int p )
@@ -430,6 +435,35 @@ __global__ void __launch_bounds__( 64 ) k_gv( const GVParams P )
 		// four elements whatever the channel count (what lies behind a pixel is
 		// the next pixel, inside the slot), the padding selected to zero after:
 		// no branch per channel in a loop body that is unrolled 32 times
+		if constexpr( F16K )
+		{
+			// half: v_cvt_f32_f16 (denormals kept); bfloat16: bits << 16 --
+			// exact for every bit pattern, what k_pack writes (generic.hip)
+			unsigned short e[ 4 ];
+#pragma unroll
+			for( int c = 0; c < 4; c++ )
+			{
+				e[ c ] = ((const unsigned short*) rp )[ c ];
+			}
+
+			if( raw_kind == 4 )
+			{
+#pragma unroll
+				for( int c = 0; c < 4; c++ )
+				{
+					v[ c ] = (float) __builtin_bit_cast( _Float16, e[ c ]);
+				}
+			}
+			else
+			{
+#pragma unroll
+				for( int c = 0; c < 4; c++ )
+				{
+					v[ c ] = __uint_as_float( (unsigned int) e[ c ] << 16 );
+				}
+			}
+		}
+		else
 		if( raw_kind == 1 )
 		{
 #pragma unroll
@@ -707,6 +741,11 @@ __global__ void __launch_bounds__( 64 ) k_gv( const GVParams P )
 	if( P.ax.lanc != 4 ) GV_LAUNCH_L1( NT, RW, 2, 3 ); \
 	else GV_LAUNCH_L1( NT, RW, 2, 2 ); } while( 0 )
 
+// (half / bfloat16 pixels: gpassv_lancraw16.hip)
+#define GV_LAUNCH_LR16( NT, RW ) do { \
+	if( P.ax.lanc != 4 ) GV_LAUNCH_L1( NT, RW, 2, 11 ); \
+	else GV_LAUNCH_L1( NT, RW, 2, 10 ); } while( 0 )
+
 // (uint8 pixels: gpassv_lancraw8.hip)
 #define GV_LAUNCH_LR8( NT, RW ) do { \
 	if( P.ax.lanc != 4 ) GV_LAUNCH_L1( NT, RW, 2, 7 ); \
@@ -720,6 +759,8 @@ int launch_gv_lanc( const GVParams& P, int wp, int items, size_t lds,
 int launch_gv_lanc_raw( const GVParams& P, int items, size_t lds,
 	hipStream_t st );
 int launch_gv_lanc_raw8( const GVParams& P, int items, size_t lds,
+	hipStream_t st );
+int launch_gv_lanc_raw16( const GVParams& P, int items, size_t lds,
 	hipStream_t st );
 void launch_gv_post( const GVParams& P, int wp, int items, size_t lds,
 	hipStream_t st );

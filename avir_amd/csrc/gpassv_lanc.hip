@@ -11,8 +11,12 @@ int launch_gv_lanc( const GVParams& P, int wp, int items, size_t lds,
 
 	if( wp == 2 && P.raw != nullptr )
 	{
+		// (every group names the kinds its loader knows)
 		return( P.raw_kind == 1 ? launch_gv_lanc_raw8( P, items, lds, st ) :
-			launch_gv_lanc_raw( P, items, lds, st ));
+			P.raw_kind == 2 || P.raw_kind == 3 ?
+			launch_gv_lanc_raw( P, items, lds, st ) :
+			P.raw_kind == 4 || P.raw_kind == 5 ?
+			launch_gv_lanc_raw16( P, items, lds, st ) : 1 );
 	}
 
 	switch( nt )

@@ -52,15 +52,15 @@ namespace avirhip {
 // (copyScanline*v's cast and zero padding, lancir.h:1406-1594); the host only
 // picks these for dword-aligned bases and pitches (lfuse_takes_raw).
 // SRC = 0: float RGBA; 1: uint8 pixels (always one DMA instruction); 2 .. 4: any
-// raw kind with SRC - 1 instructions. OUTK: the output stage's compile-time
-// kind (gp_store_lancir_row; 0 = whatever P.lout says).
+// raw kind with SRC - 1 instructions; 5, 6: half / bfloat16 (lfuse_launch16
+// below). OUTK: gp_store_lancir_row's kind (0 = whatever P.lout says).
 // LORD: the summation order at compile time (3, 4), or 0 = the axis' own.
 template< int SRC, int OUTK, int LORD >
 __global__ void __launch_bounds__( 64 ) k_lf( const LFParams P )
 {
 	constexpr bool RAW = ( SRC > 0 );
-	constexpr int TDN = ( SRC <= 1 ? SRC : SRC - 1 );
-	const int raw_kind = ( SRC == 1 ? 1 : P.raw_kind );
+	constexpr int TDN = ( SRC <= 1 ? SRC : ( SRC >= 5 ? SRC - 4 : SRC - 1 ));
+	const int raw_kind = ( SRC == 1 ? 1 : ( SRC >= 5 ? 2 : P.raw_kind ));
 	constexpr int NT = 6;   // taps of both kernels (la = 3, upsizing)
 	constexpr int NTP = 8;  // ... padded to whole f4 rows
 	constexpr int RW = 8;   // vertical window (ring slots, >= NT)
@@ -169,7 +169,7 @@ __global__ void __launch_bounds__( 64 ) k_lf( const LFParams P )
 #pragma unroll
 			for( int c = 0; c < 4; c++ )
 			{
-				v[ c ] = (float) ((const unsigned short*) rp )[ c ];
+				v[ c ] = gp_elem16< ( SRC >= 5 ) >( rp, c, P.raw_kind );
 			}
 		}
 		else
@@ -426,7 +426,7 @@ int lfuse_launch( LFParams& P, hipStream_t st )
 		src_kind <= 1 && lord == 4 ) ? lord : 0 );
 
 #define LF_GO( S, O, L ) hipLaunchKernelGGL(( k_lf< S, O, L > ), grid, dim3( 64 ), lds, st, P )
-	switch( src_kind * 100 + out_kind * 10 + lk )
+	switch( lf_is16( P ) ? -1 : src_kind * 100 + out_kind * 10 + lk )
 	{
 		case 0: LF_GO( 0, 0, 0 ); break;
 		case 4: LF_GO( 0, 0, 4 ); break;
@@ -443,7 +443,7 @@ int lfuse_launch( LFParams& P, hipStream_t st )
 		case 200: LF_GO( 2, 0, 0 ); break;
 		case 300: LF_GO( 3, 0, 0 ); break;
 		case 400: LF_GO( 4, 0, 0 ); break;
-		default: return( 1 );
+		default: return( lfuse_launch16( P, grid, lds, st ));
 	}
 #undef LF_GO
 
@@ -453,7 +453,7 @@ int lfuse_launch( LFParams& P, hipStream_t st )
 
 // Whether k_lf can read the owner's image as it is: dword-aligned base and row
 // pitch (a segment starts at the dword at or below its first pixel), byte
-// offsets in 31 bits.
+// offsets in 31 bits, an element type row_px knows (gp_raw_kind).
 bool lfuse_takes_raw( const ImageRef& img, int in_len_v, int width )
 {
 	const long esz = (long) dtype_size( img.type );
@@ -461,7 +461,55 @@ bool lfuse_takes_raw( const ImageRef& img, int in_len_v, int width )
 	return( img.ptr != nullptr && ( (uintptr_t) img.ptr & 3 ) == 0 &&
 		(( img.stride * esz ) & 3 ) == 0 &&
 		image_dma_bytes( img, in_len_v, width ) != 0 &&
-		img.ch >= 1 && img.ch <= 4 && esz * img.ch < 16 );
+		img.ch >= 1 && img.ch <= 4 && esz * img.ch < 16 &&
+		gp_raw_kind( img.type ) != 0 );
+}
+
+// The variants for half / bfloat16 images (lf_is16: a 16-bit float source read
+// raw, or a 16-bit float result), kernels of their own so that the ones above
+// stay the code they were. Source: SRC 5 / 6 -- P.raw_kind 4 / 5 with one / two
+// DMA instructions a segment; inside the kernel `raw_kind` is 2, uint16's
+// geometry throughout (bytes per pixel, row pitch, segment, range), and
+// gp_elem16 widens where a uint16 element is cast: half by v_cvt_f32_f16
+// (denormals kept), bfloat16 by bits << 16 -- what the pack pass writes.
+// Result: store kind 3 behind every source kind (gp_store_lancir_f16: the gain,
+// nearest-even narrowing, no clamp), kind 0 for the uint8 / uint16 / float
+// result of a 16-bit source. The summation order is the axis' own (LORD 0).
+// 1: no variant takes the call (an element type no kernel knows).
+int lfuse_launch16( const LFParams& P, const dim3 grid, const size_t lds,
+	hipStream_t st )
+{
+	const bool src16 = ( P.raw != nullptr && P.raw_kind >= 4 );
+	const bool out16 = ( P.lout.on != 0 &&
+		dtype_is_float16_kind( P.lout.type ));
+	const int src_kind = ( P.raw == nullptr ? 0 : ( P.raw_kind == 1 ? 1 :
+		P.raw_tdn + ( src16 ? 4 : 1 )));
+
+	if(( P.raw != nullptr && ( P.raw_kind < 1 || P.raw_kind > 5 )) ||
+		( P.lout.on != 0 && !out16 && P.lout.type != AVIRHIP_U8 &&
+		P.lout.type != AVIRHIP_U16 && P.lout.type != AVIRHIP_F32 ))
+	{
+		return( 1 );
+	}
+
+#define LF_GO( S, O ) hipLaunchKernelGGL(( k_lf< S, O, 0 > ), grid, dim3( 64 ), lds, st, P )
+	switch( src_kind * 10 + ( out16 ? 3 : 0 ))
+	{
+		case 3: LF_GO( 0, 3 ); break;
+		case 13: LF_GO( 1, 3 ); break;
+		case 23: LF_GO( 2, 3 ); break;
+		case 33: LF_GO( 3, 3 ); break;
+		case 43: LF_GO( 4, 3 ); break;
+		case 50: LF_GO( 5, 0 ); break;
+		case 53: LF_GO( 5, 3 ); break;
+		case 60: LF_GO( 6, 0 ); break;
+		case 63: LF_GO( 6, 3 ); break;
+		default: return( 1 );
+	}
+#undef LF_GO
+
+	AVIRHIP_HIPCHECK( hipGetLastError() );
+	return( AVIRHIP_OK );
 }
 
 } // namespace avirhip

@@ -353,6 +353,16 @@ inline int image_dma_bytes( const ImageRef& img, const int rows,
 		0 );
 }
 
+// The kind of a raw source's elements as the loaders that move rows as bytes
+// name it (k_lf's row_px, k_gv's raw_px): 1 uint8, 2 uint16, 3 float, 4 half,
+// 5 bfloat16; 0: a type no such loader knows (double, uint32) -- the ONE list
+// behind lfuse_takes_raw and gpass_v_raw_ok.
+inline int gp_raw_kind( const int t )
+{
+	return( t == AVIRHIP_U8 ? 1 : t == AVIRHIP_U16 ? 2 : t == AVIRHIP_F32 ? 3 :
+		t == AVIRHIP_F16 ? 4 : t == AVIRHIP_BF16 ? 5 : 0 );
+}
+
 int finalize_avir_plan( avirhip_plan* p ); // api.cpp
 // device bytes a plan holds, with its inner plan, same-device spares and
 // other-device replicas (the plan caches' byte bound)

@@ -73,8 +73,15 @@ typedef enum avirhip_dtype {
  * 1-4 channels: k_gh reads a half source where it lies, and the last pass
  * -- k_gv, k_gf, the accumulation kernels k_sacc* -- narrows and stores a half
  * result; an axis that streams (k >= 2), k_gf and k_gh2 read the pack pass's
- * float copy of the source. Everywhere else -- the tiles, gamma, CLancIR's
- * other ratios -- the pack pass widens and the output stage narrows.) */
+ * float copy of the source. CLancIR's pass kernels do the same at its other
+ * ratios, 1-4 channels: k_lf (upsizing, one launch) and k_gv read a half
+ * source where it lies -- dword-aligned base and row pitch, more than 48
+ * columns, up to 24 taps -- and k_lf / k_gh apply the gain, narrow and store a
+ * half result at any even address; an image they cannot take goes through
+ * the pack pass / the output stage with the same bits. Everywhere else -- the
+ * tiles, gamma, CLancIR's exact-2x calls with 1-3 channels or an integer
+ * result behind a half source, its generic kernels -- the pack pass widens
+ * and the output stage narrows.) */
 	AVIRHIP_F16 = 5,
 	/* bfloat16 elements: 16 bits holding the upper half of an IEEE binary32.
 	 * A call with bfloat16 elements is DEFINED by the same call with float
@@ -95,7 +102,8 @@ typedef enum avirhip_dtype {
 	 * CLancIR accepts them on either side under the same rule. (k_up2, k_dnfh
  * and k_lanc2h read and store bfloat16 RGBA pixels themselves, as they do
  * half ones, and so do the pass kernels -- k_gh the source, k_gv / k_gf /
- * k_sacc* the result, 1-4 channels -- at every other ratio.) */
+ * k_sacc* the result, 1-4 channels -- at every other ratio, and CLancIR's:
+ * k_lf / k_gv the source, k_lf / k_gh the result.) */
 	AVIRHIP_BF16 = 6
 } avirhip_dtype;
 
@@ -326,8 +334,8 @@ int avirhip_plan_get_path(const avirhip_plan* plan);
  * result is narrowed and stored by it. With AVIRHIP_VARIANT_UPG_TWO_PASS k_gh
  * reads such a source where it lies. The environment variable
  * AVIRHIP_GP_NO_IO16, read per call, puts the pack pass and the output stage
- * around the pass kernels for every half / bfloat16 image: A/B timing and
- * differential tests.) */
+ * around the pass kernels for every half / bfloat16 image, CLancIR's
+ * included: A/B timing and differential tests.) */
 #define AVIRHIP_VARIANT_UPG_FUSED 16
 /* float RGBA sources on downsizing axes: the branch-free accumulation kernels
  * run optimistically (exact kernels behind an alarm) as they do for float

@@ -39,10 +39,21 @@ stage: the road before the typed k_gh and the narrowing store), and the typed
 k_gh forced where k_gf / k_gh2 keep the pack pass; with PARENT.so also RGB
 uint8 on both builds (the store function the integer stage shares).
 
-usage: python tools/half_timing.py [--bf16 | --lancir | --dnf | --gpass]
-       [PARENT.so] [REPS=5] [ONLY]
-(ONLY, with --gpass: the shapes whose names hold one of these comma-separated
-words, e.g. "u8")"""
+--lancgp measures CLancIR at general ratios (path 5: k_lf, or k_gv + k_gh) by
+the same method -- 1920x1080 -> 2500x1400, 3840x2160 -> 1280x720, 1920x1080 ->
+5760x3240, RGBA half and bfloat16 in and out, plus RGB half at the first shape
+-- as float32, the 16-bit call as it runs automatically (the fused road: the
+raw loaders' kinds 4 / 5 and gp_store_lancir_row< 3 >) and the same call with
+AVIRHIP_VARIANT_UP2_UNFUSED_IO (pack pass, kernels, output stage: the road
+before). Then the `lf_pays` sweep: k_lf (AVIRHIP_VARIANT_UPG_FUSED) against
+k_gv + k_gh (AVIRHIP_VARIANT_UPG_TWO_PASS) with a half RGBA result at x1.5,
+x2.5, x3 and x4 from 1920x1080. With PARENT.so also README's CLancIR rows of
+uint8 / float32 images on both builds, alternating.
+
+usage: python tools/half_timing.py [--bf16 | --lancir | --dnf | --gpass |
+       --lancgp] [PARENT.so] [REPS=5] [ONLY]
+(ONLY, with --gpass and --lancgp: the shapes whose names hold one of these
+comma-separated words, e.g. "u8")"""
 import ctypes as C
 import hashlib
 import os
@@ -401,7 +412,135 @@ def gpass_main(argv):
         torch.cuda.empty_cache()
 
 
+def lancgp_main(argv):
+    """--lancgp: the rows of the module docstring, CLancIR plans on their
+    automatic path (5 at every shape below)."""
+    import numpy as np
+    import torch
+    import avir_amd
+    from avir_amd import abi, synth
+    parent = argv[1] if len(argv) > 1 and argv[1] != "-" else None
+    reps = int(argv[2]) if len(argv) > 2 else 5
+    only = argv[3].split(",") if len(argv) > 3 else None
+    lib = abi.load()
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    header(lib, parent)
+    TD = {abi.F32: torch.float32, abi.F16: torch.float16,
+          abi.BF16: torch.bfloat16, abi.U8: torch.uint8}
+    ES = {abi.F32: 4, abi.F16: 2, abi.BF16: 2, abi.U8: 1}
+    F32, F16, BF16, U8 = abi.F32, abi.F16, abi.BF16, abi.U8
+    U = abi.VARIANT_UP2_UNFUSED_IO
+    VF, V2 = abi.VARIANT_UPG_FUSED, abi.VARIANT_UPG_TWO_PASS
+
+    def both(tag, ti, to, ch=4):
+        return [("%s fused (automatic)" % tag, lib, ti, to, ch, 0),
+                ("%s pack + output stage" % tag, lib, ti, to, ch, U)]
+
+    f32 = [("f32->f32", lib, F32, F32, 4, 0)]
+    shapes = [
+        ("1080p x1.3", (1920, 1080, 2500, 1400),
+         f32 + both("f16->f16", F16, F16) + both("bf16->bf16", BF16, BF16) +
+         both("RGB f16->f16", F16, F16, 3)),
+        ("4K k3", (3840, 2160, 1280, 720),
+         f32 + both("f16->f16", F16, F16) + both("bf16->bf16", BF16, BF16)),
+        ("1080p x3", (1920, 1080, 5760, 3240),
+         f32 + both("f16->f16", F16, F16) + both("bf16->bf16", BF16, BF16)),
+    ]
+    for name, (nw, nh) in (("sweep x1.5", (2880, 1620)),
+                           ("sweep x2.5", (4800, 2700)),
+                           ("sweep x3", (5760, 3240)),
+                           ("sweep x4", (7680, 4320))):
+        shapes.append((name, (1920, 1080, nw, nh),
+                       [("f16->f16 k_lf", lib, F16, F16, 4, VF),
+                        ("f16->f16 k_gv + k_gh", lib, F16, F16, 4, V2),
+                        ("f32->f16 k_lf", lib, F32, F16, 4, VF),
+                        ("f32->f16 k_gv + k_gh", lib, F32, F16, 4, V2)]))
+    if parent:
+        P = abi.load_path(parent)
+
+        def ab(ti, ch):
+            return [("this build", lib, ti, ti, ch, 0),
+                    ("parent build", P, ti, ti, ch, 0),
+                    ("this build again", lib, ti, ti, ch, 0)]
+        shapes += [
+            ("parent 5184 RGB u8", (5184, 3456, 1920, 1280), ab(U8, 3)),
+            ("parent 4K k3 RGBA u8", (3840, 2160, 1280, 720), ab(U8, 4)),
+            ("parent 1080p x1.3 RGB u8", (1920, 1080, 2500, 1400), ab(U8, 3)),
+            ("parent 1080p x1.3 RGBA u8", (1920, 1080, 2500, 1400), ab(U8, 4)),
+            ("parent 1080p x1.3 RGBA f32", (1920, 1080, 2500, 1400),
+             ab(F32, 4))]
+    for name, (sw, sh, nw, nh), rows in shapes:
+        if only is not None and not any(o in name for o in only):
+            continue
+        base = synth.lcg_f32((sh, sw, 4))
+        run, keep, first = {}, [], {}
+        for tag, L, ti, to, ch, variant in rows:
+            pair = sw * sh * ch * ES[ti] + nw * nh * ch * ES[to]
+            n = max(2, -(-(512 << 20) // pair))
+            ring = []
+            for i in range(n):
+                b = np.roll(base, i, axis=0)[:, :, :ch]
+                if ti == U8:
+                    b = b * 255.0
+                s = torch.from_numpy(np.ascontiguousarray(b)).to(dev).to(TD[ti])
+                d = torch.empty((nh, nw, ch), dtype=TD[to], device=dev)
+                ring.append((s, d))
+            with abi.using(L):
+                r = avir_amd.CLancIR()
+                p = r.plan(sw, sh, nw, nh, ch, None, ti, to)
+            if variant:
+                abi.check(L.avirhip_plan_set_variant(p, variant), "variant")
+            keep.append((r, ring))
+
+            def once(L=L, p=p, ring=ring):
+                t = 0.0
+                ms = C.c_double()
+                for s, d in ring:
+                    abi.check(L.avirhip_time_resize(
+                        p, s.data_ptr(), d.data_ptr(), 1, st, C.byref(ms)),
+                        "time_resize")
+                    t += ms.value
+                return t / len(ring)
+            run[tag] = (once, pair, n, L, p)
+            first[tag] = ring[0][1]
+        for tag in run:  # warm-up, clocks
+            for _ in range(10):
+                run[tag][0]()
+        torch.cuda.synchronize()
+        res = {tag: [] for tag in run}
+        loops = 20
+        for _ in range(reps):
+            for tag in run:
+                res[tag].append(sum(run[tag][0]() for _ in range(loops)) / loops)
+        print("%s (%dx%d -> %dx%d, CLancIR), path %d, %d reps x %d ring "
+              "passes:" % (name, sw, sh, nw, nh,
+                           lib.avirhip_plan_get_path(run[rows[0][0]][4]),
+                           reps, loops))
+        for tag in run:
+            v = sorted(res[tag])
+            med = v[len(v) // 2]
+            print("  %-36s %.4f ms  (min %.4f max %.4f)  %6.1f MB/call  "
+                  "ring %d  plan holds %.1f MB" % (
+                      tag, med, v[0], v[-1], run[tag][1] / 1e6, run[tag][2],
+                      run[tag][3].avirhip_plan_device_bytes(run[tag][4]) / 1e6),
+                  flush=True)
+        tags = list(run)
+        for i in range(0, len(tags) - 1):
+            a, b = tags[i], tags[i + 1]
+            if (a.split(" fused")[0] == b.split(" pack")[0] or
+                    a.split(" k_lf")[0] == b.split(" k_gv")[0] or
+                    a == "this build"):
+                print("  %s / %s bit-identical: %s" % (a, b, torch.equal(
+                    first[a].view(torch.uint8), first[b].view(torch.uint8))),
+                    flush=True)
+        del keep, run, first
+        torch.cuda.empty_cache()
+
+
 def main():
+    if "--lancgp" in sys.argv:
+        return lancgp_main([a for a in sys.argv if a != "--lancgp"])
     if "--gpass" in sys.argv:
         return gpass_main([a for a in sys.argv if a != "--gpass"])
     if "--lancir" in sys.argv:

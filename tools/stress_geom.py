@@ -25,7 +25,11 @@ usage: python tools/stress_geom.py [cases=120] [seed=1] [repeats=4]
            [--against LIB.so] [--lib LIB.so] [--family F] [--chunks]
   --lib      the library under test (default: the product build / AVIRHIP_LIB)
   --family   all | up2 | lanc2 | lanc2h | dnf | dnfh | gpass_up | gf | lf |
-             lanc_dn | sacc
+             lanc_dn | sacc | lancgp16
+             (lancgp16: CLancIR at general ratios with half / bfloat16 pixels
+             on a side -- the raw loaders' kinds 4 / 5 of k_lf and k_gv, the
+             narrowing store of k_lf and k_gh -- always with forced
+             AVIRHIP_LF_CHUNK / AVIRHIP_GV_CHUNK; no part of `all`)
              (geometries that route to one kernel family; the summary counts the
              execution paths that actually ran)
   --chunks   force a random chunk length per case: below, at and above the ring
@@ -45,9 +49,14 @@ CHUNK_ENVS = ("AVIRHIP_GV_CHUNK", "AVIRHIP_GH_CHUNK", "AVIRHIP_GF_CHUNK",
               "AVIRHIP_LF_CHUNK", "AVIRHIP_SA_CHUNK", "AVIRHIP_UP2_CQ",
               "AVIRHIP_LANC2_CQ", "AVIRHIP_DNF_CROWS")
 FAMILIES = ("all", "up2", "lanc2", "lanc2h", "dnf", "dnfh", "gpass_up", "gf",
-            "lf", "lanc_dn", "sacc")
+            "lf", "lanc_dn", "sacc", "lancgp16")
 BF16 = "bfloat16"  # (numpy has no such type: the name stands for it)
 # k_lanc2h's (SRC, OUT) pairs: every one but float -> float
+# CLancIR's pass kernels with a 16-bit float type on a side (lancgp16)
+LANCGP16_PAIRS = [(a, b) for a in (np.float16, BF16, np.float32, np.uint8,
+                                   np.uint16)
+                  for b in (np.float16, BF16, np.float32, np.uint8, np.uint16)
+                  if a in (np.float16, BF16) or b in (np.float16, BF16)]
 LANC2H_PAIRS = [(a, b) for a in (np.float16, BF16, np.float32)
                 for b in (np.float16, BF16, np.float32)
                 if not (a is np.float32 and b is np.float32)]
@@ -143,6 +152,24 @@ def gen_case(rng, family, big):
         kx = float(rng.uniform(0.15, 0.95))
         ky = kx * float(rng.uniform(0.85, 1.2))
         nw, nh = max(16, int(sw * kx)), max(16, int(sh * min(0.97, ky)))
+    elif family == "lancgp16":
+        # CLancIR, any ratio but exact 2x, upsizing (k_lf, or k_gv + k_gh under
+        # the variant bits) and downsizing up to 24 taps (k_gv + k_gh), half /
+        # bfloat16 pixels on a side; mostly same-type RGBA, row pitches of 1-3
+        # channel images a multiple of 4 bytes (read raw) or not (pack pass)
+        lanc = True
+        kx = float(rng.uniform(1.02, 3.4)) if rng.rand() < 0.5 else \
+            float(rng.uniform(0.26, 0.95))
+        ky = kx * float(rng.uniform(0.85, 1.2))
+        ky = max(1.02, ky) if kx > 1 else min(0.97, ky)
+        nw, nh = max(16, int(sw * kx)), max(16, int(sh * ky))
+        if nw == 2 * sw and nh == 2 * sh:
+            nw += 1
+        ch = int(rng.choice([4, 4, 4, 3, 3, 1, 2]))
+        if rng.rand() < 0.7:
+            tin = tout = (np.float16, BF16)[rng.randint(0, 2)]
+        else:
+            tin, tout = LANCGP16_PAIRS[rng.randint(0, len(LANCGP16_PAIRS))]
     elif family == "sacc":
         # AVIR downsizing by k > 1, not a whole number: the streaming-
         # accumulation kernels (integer sources: branch-free forms; float RGBA:
@@ -237,7 +264,7 @@ def main():
         for e in CHUNK_ENVS:
             os.environ.pop(e, None)
         chunk_note = ""
-        if args.chunks and rng.rand() < 0.75:
+        if args.family == "lancgp16" or (args.chunks and rng.rand() < 0.75):
             c = int(rng.choice([3, 4, 5, 6, 7, 8, 9, 11, 12, 13, 16, 17, 24, 33]))
             for e in ("AVIRHIP_GV_CHUNK", "AVIRHIP_GH_CHUNK", "AVIRHIP_GF_CHUNK",
                       "AVIRHIP_LF_CHUNK"):
