@@ -1210,7 +1210,9 @@ static int avir_fast( avirhip_plan* p, const int path, AvirSrc& S, void* dst,
 	// a half / bfloat16 source k_gh's typed loader takes (path 5): elements
 	// are loaded whole, four at a time -- a base that is a multiple of their
 	// size, at least four of them up to the end of the last source row the
-	// band's first pass reads (run_h's `raw_elems`); any row pitch
+	// band's first pass reads (run_h's `raw_elems`); any row pitch. The
+	// accumulation kernels' typed loaders (a horizontal axis with k >= 2,
+	// gpass.hip: sa16_wanted, asked through gpass_takes_raw) take the same
 	const bool raw16 = ( io16 && dtype_is_float16_kind( p -> in_type ) &&
 		( (uintptr_t) S.img & 1 ) == 0 && row1 > row0 &&
 		(long) gpass_last_src_row( p, row0, row1 ) * p -> src_stride +

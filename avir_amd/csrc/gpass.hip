@@ -1011,6 +1011,9 @@ bool gpass_ok( const avirhip_plan* p )
 // then 12-tap gather) from a float RGBA source -- integer sources keep the
 // tiled kernels, whose loader converts them in place of a pack pass, and the
 // long-tap downsizing chains are still faster there too.
+static bool sa16_wanted( const avirhip_plan* p, const GPData* D );
+static long sa16_auto_minpix();
+
 bool gpass_preferred( const avirhip_plan* p )
 {
 	const GPData* D = (const GPData*) p -> gpass;
@@ -1053,6 +1056,15 @@ bool gpass_preferred( const avirhip_plan* p )
 		sa_wanted( D -> sa_h, p -> io_ch == 4, p -> io_ch == 4 ) &&
 		sa_wanted( D -> sa_v, p -> io_ch == 4, p -> io_ch == 4 ) &&
 		(long) p -> src_w * p -> src_h >= 6000000L )
+	{
+		return( true );
+	}
+
+	// ... and half / bfloat16 sources the accumulation kernels read where they
+	// lie (sa16_wanted), both axes theirs: no pack pass, no float copy
+	if( D -> sa_h != nullptr && D -> sa_v != nullptr && !zs_axes &&
+		sa16_wanted( p, D ) && !fused_dn_both( p ) &&
+		(long) p -> src_w * p -> src_h >= sa16_auto_minpix() )
 	{
 		return( true );
 	}
@@ -1442,12 +1454,14 @@ bool gpass_lancir_takes_raw( const avirhip_plan* p, const ImageRef& img )
 // Whether the first pass reads the caller's image as it is (integer types,
 // 1-4 channels): AVIR plans whose horizontal axis streams (sacc.hip).
 //
-// Half / bfloat16 sources (1-4 channels): k_gh's typed loader alone knows them
-// (gp_load_raw kinds 4, 5), so the horizontal axis must run the gather kernels
-// with a source segment of at most four pieces and must not be one the
-// accumulation kernels want -- that axis keeps the pack pass, k_sacc* reads
-// uint8, uint16 and float elements only. Two classes of call whose float RGBA
-// kernels have no typed form keep the pack pass as well (io16_prefers_pack).
+// Half / bfloat16 sources (1-4 channels): k_gh's typed loader knows them
+// (gp_load_raw kinds 4, 5) -- the horizontal axis runs the gather kernels with
+// a source segment of at most four pieces --, and so do k_sacc / k_sacc2
+// (typed loaders 4, 5) where the horizontal axis is theirs with k >= 2 and the
+// frame is at or above the floor (sa16_wanted); under the floor the pack pass
+// stays in front of them, and a zero-stuffed 1 < k < 2 axis is the gather
+// kernels'. Two classes of call whose float RGBA kernels have no typed form
+// keep the pack pass as well (io16_prefers_pack).
 // AVIRHIP_GP_NO_IO16 (read per call): the pack pass and the output stage for
 // every 16-bit image on this path -- A/B timing, differential tests.
 bool gpass_io16()
@@ -1514,6 +1528,73 @@ static bool io16_prefers_pack( const avirhip_plan* p, const GPData* D )
 	return( false );
 }
 
+// Frames of fewer source pixels keep the pack pass in front of a half /
+// bfloat16 source of the accumulation kernels: their float copy is under
+// 1 MiB, nothing to gain (AVIRHIP_SA16_MINPIX: a tuning aid, read by the first
+// call of any plan).
+static long sa16_minpix()
+{
+	static const long v = ( getenv( "AVIRHIP_SA16_MINPIX" ) != nullptr ?
+		atol( getenv( "AVIRHIP_SA16_MINPIX" )) : 65536L );
+
+	return( v );
+}
+
+// Whether k_sacc / k_sacc2 read a half / bfloat16 source where it lies (typed
+// loaders 4 / 5, row lanes): the horizontal axis is theirs with k >= 2 (not the
+// zero-stuffed 1 < k < 2 form, which keeps k_gh / k_gh2), rows of at least one
+// group of the exact form, no gamma, the frame at or above the floor. The ONE
+// predicate of this road: gpass_takes_raw (and through it api.cpp's `raw`),
+// route_avir and gpass_preferred ask it.
+static bool sa16_wanted( const avirhip_plan* p, const GPData* D )
+{
+	return( D != nullptr && !p -> is_lancir && !p -> gamma && gpass_io16() &&
+		dtype_is_float16_kind( p -> in_type ) && D -> sa_h != nullptr &&
+		!sacc_is_zs( D -> sa_h ) && p -> src_w >= 4 &&
+		(long) p -> src_w * p -> src_h >= sa16_minpix() );
+}
+
+// Measured in one process, the roads alternating over a ring of buffers, same-
+// type half pixels (tools/half_timing.py --sacc, NOTEBOOK 28; bfloat16 within
+// 0.003, spread of repeated runs under 0.003; ms):
+//                          forced path 5                        automatic
+//   RGBA                   typed exact / optimistic / pack road  tiles / path 5
+//   5184x3456 -> 1920x1280  0.190 / 0.189 / 0.285                0.351 / 0.187
+//   3840x2160 -> 1500x844   0.111 / 0.125 / 0.156                0.169 / 0.110
+//   3200x1800 -> 1200x675   0.103 / 0.104 / 0.137                0.129 / 0.102
+//   2560x1440 -> 1000x563   0.082 / 0.095 / 0.104                0.093 / 0.082
+//   1920x1080 -> 700x394    0.072 / 0.083 / 0.085                0.063 / 0.073
+//   640x480 -> 233x175      0.053 / 0.059 / 0.055                0.031 / 0.053
+//   320x240 -> 117x88       0.052 / 0.058 / 0.053                --
+//   RGB
+//   5184x3456 -> 1920x1280  0.206 / 0.179 / 0.287                0.358 / 0.206
+//   3840x2160 -> 1500x844   0.117 / 0.115 / 0.155                0.169 / 0.118
+//   3200x1800 -> 1200x675   0.106 / 0.097 / 0.136                0.131 / 0.106
+//   2560x1440 -> 1000x563   0.082 / 0.086 / 0.101                0.093 / 0.083
+//   1920x1080 -> 700x394    0.073 / 0.076 / 0.086                0.065 / 0.073
+//   640x480 -> 233x175      0.051 / 0.055 / 0.054                0.031 / 0.051
+// The typed exact road is ahead of the pack road at every size down to the
+// floor. The automatic path (gpass_preferred) takes such a source, both axes
+// on the accumulation kernels, where path 5 is ahead of the tiles: it is at
+// 3,686,400 source pixels and is not at 2,073,600.
+// AVIRHIP_SA16_AUTO_MINPIX (read when a plan is made): A/B timing.
+static long sa16_auto_minpix()
+{
+	const char* const e = getenv( "AVIRHIP_SA16_AUTO_MINPIX" );
+
+	return( e != nullptr ? atol( e ) : 3600000L );
+}
+
+// Whether such a source runs optimistically without being asked to
+// (AVIRHIP_VARIANT_SACC_OPTIMISTIC forces it at any size): RGBA never -- the
+// exact kernel is as fast or faster at every size, as for float RGBA; pixels
+// of 1-3 channels (measured as RGB) from 5,500,000 source pixels on -- ahead
+// at 5,760,000, behind at 3,686,400.
+static bool sa16_optimistic( const avirhip_plan* p )
+{
+	return( p -> io_ch < 4 && (long) p -> src_w * p -> src_h >= 5500000L );
+}
+
 bool gpass_takes_raw( const avirhip_plan* p )
 {
 	const GPData* D = (const GPData*) p -> gpass;
@@ -1522,9 +1603,10 @@ bool gpass_takes_raw( const avirhip_plan* p )
 
 	if( dtype_is_float16_kind( p -> in_type ))
 	{
-		return( D != nullptr && !p -> is_lancir && !p -> gamma && gpass_io16() &&
+		return( sa16_wanted( p, D ) ||
+			( D != nullptr && !p -> is_lancir && !p -> gamma && gpass_io16() &&
 			h_gather_takes( D, true ) && !sa_wanted( D -> sa_h, true, true ) &&
-			!io16_prefers_pack( p, D ));
+			!io16_prefers_pack( p, D )));
 	}
 
 	// (the loaders of the accumulation kernels know uint8, uint16 and float
@@ -1565,6 +1647,7 @@ static GPLOut gp_make_lout( const avirhip_plan* p, const LancirOut& o )
 //                           stage on k_gv rings too long for whole-pixel lanes
 //   optimistic     AVIR     a float source that is not float RGBA (or       k_sacc2v x2,
 //                           SACC_OPTIMISTIC), both axes on the branch-free   k_sacc x2
+//                           (half / bfloat16: sa16_optimistic; k_sacc2 first)
 //                           accumulation kernels, no SACC_LADDER
 //   avir two-pass  AVIR     otherwise: per axis the accumulation kernels    k_sacc* or k_gh /
 //                           (exact; integer sources: finite, or ladder)     k_gh2, k_sacc* or
@@ -1682,23 +1765,28 @@ static GPRoute route_avir( const avirhip_plan* p, const GPData* D,
 	// and the two launches behind the alarm cost 9 us a frame. Float pixels of
 	// 1-3 channels gain: 0.273 -> 0.198 ms for the same frame as float RGB.
 	static const bool no_opt = ( getenv( "AVIRHIP_NO_SACC_OPT" ) != nullptr );
-	const bool fsrc = ( raw != nullptr ? raw -> type == AVIRHIP_F32 : true );
+	const bool fsrc0 = ( raw != nullptr ? raw -> type == AVIRHIP_F32 : true );
 	static const bool opt_rgba = ( getenv( "AVIRHIP_SACC_OPT_RGBA" ) != nullptr &&
 		atoi( getenv( "AVIRHIP_SACC_OPT_RGBA" )) != 0 ); // (tuning aid)
-	// A half / bfloat16 source read raw (gpass_takes_raw: its horizontal axis
-	// is k_gh's): a float source that can be non-finite -- never GPA_FINITE, no
-	// integer shortcut -- and none the accumulation kernels read, so it never
-	// runs optimistically either (`fsrc`). Its vertical pass reads the float
+	// A half / bfloat16 source read raw (gpass_takes_raw): a float source that
+	// can be non-finite -- never GPA_FINITE, no integer shortcut. Its horizontal
+	// axis is k_gh's, or (`sa16`, sa16_wanted) the accumulation kernels': the
+	// exact k_sacc< 4 / 5 > alone by default, two launches; optimistically --
+	// k_sacc2< 4 / 5 > first -- where AVIRHIP_VARIANT_SACC_OPTIMISTIC asks, as
+	// for float RGBA (sa16_optimistic). Its vertical pass reads the float
 	// RGBA rows of `mid` and is classified as the pack pass's float RGBA
 	// source is.
 	const bool h16 = ( raw != nullptr && dtype_is_float16_kind( raw -> type ));
+	const bool sa16 = ( h16 && sa16_wanted( p, D ));
+	const bool fsrc = ( fsrc0 || sa16 );
 	const bool frgba = ( raw == nullptr || h16 );
 	const bool opt_wanted = (( raw != nullptr && !h16 ) || opt_rgba ||
-		( p -> variant & AVIRHIP_VARIANT_SACC_OPTIMISTIC ) != 0 );
+		( p -> variant & AVIRHIP_VARIANT_SACC_OPTIMISTIC ) != 0 ||
+		( sa16 && sa16_optimistic( p )));
 
 	// (float RGBA -- the exact kernels unless the variant asks)
 	const bool sa_always = ( int_src || ( frgba && !opt_wanted ));
-	const bool use_sa_h = ( !h16 &&
+	const bool use_sa_h = ( h16 ? sa16 :
 		sa_wanted( D -> sa_h, sa_always, raw == nullptr ));
 	const bool use_sa_v = sa_wanted( D -> sa_v, sa_always, frgba );
 
@@ -1982,8 +2070,22 @@ static int run_avir_optimistic( const avirhip_plan* p, const GPData* D,
 	int a, b;
 	v_source_rows( D, C.row0, C.row1, a, b );
 
+	// (a half / bfloat16 source: its first pass is k_sacc2, whose sources were
+	// integers -- it has no code that lowers the alarm; the stream does it)
+	if( C.raw != nullptr && dtype_is_float16_kind( C.raw -> type ))
+	{
+		AVIRHIP_HIPCHECK( hipMemsetAsync( D -> nf_flag, 0, 4, C.st ));
+	}
+
 	int rc = avir_h_acc( p, D, C, a, b, fast );
 	if( rc == 0 ) rc = avir_v_acc( p, D, C, fast );
+
+	// (AVIRHIP_SACC_OPT_ONLY, read per call: the branch-free launches alone --
+	// what they cost, and what they leave where the alarm was due)
+	if( rc == 0 && getenv( "AVIRHIP_SACC_OPT_ONLY" ) != nullptr )
+	{
+		return( rc );
+	}
 
 	if( rc == 0 )
 	{

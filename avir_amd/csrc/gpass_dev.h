@@ -803,6 +803,45 @@ __device__ __forceinline__ float gp_elem16( const char* const rp, const int c,
 	return( kind == 4 ? (float) __builtin_bit_cast( _Float16, e ) :
 		__uint_as_float( (unsigned int) e << 16 ));
 }
+
+// The accumulation kernels' typed sources (sacc.hip, SRC: 1 uint8, 2 uint16,
+// 3 float, 4 half, 5 bfloat16): the kinds of 2-byte elements -- one geometry
+// (a group of two pixels is CH dwords, k_sacc2's eight samples 4 * CH) ...
+__host__ __device__ constexpr bool sa_src2( const int src )
+{
+	return( src == 2 || src == 4 || src == 5 );
+}
+
+// ... and an element as float: integers and floats cast, half and bfloat16
+// widened as gp_elem16< true > widens them (`e`: the element, or its 16 bits
+// in a wider word).
+template< int SRC, typename T >
+__device__ __forceinline__ float sa_elem( const T e )
+{
+	if constexpr( SRC == 4 )
+	{
+		// (the instruction itself: it reads the low half of its operand, so
+		// a word's lower element needs no mask)
+		float r;
+		asm( "v_cvt_f32_f16 %0, %1" : "=v"( r ) : "v"( (unsigned int) e ));
+		return( r );
+	}
+	else
+	if constexpr( SRC == 5 )
+	{
+		return( __uint_as_float( (unsigned int) (unsigned short) e << 16 ));
+	}
+	else
+	{
+		return( (float) e );
+	}
+}
+
+// (host) the image types of those kinds
+inline bool sa_type2( const int type )
+{
+	return( type == AVIRHIP_U16 || type == AVIRHIP_F16 || type == AVIRHIP_BF16 );
+}
 // gpass_h2.hip: k_gh2 (two gather outputs per lane); 1: no variant for the tap count
 int launch_gh2( const GHParams& P, int items, size_t lds, hipStream_t st );
 // (`img`: rows of `width` pixels, `in_len_v` of them)

@@ -93,7 +93,7 @@ struct SAParams
 
 typedef unsigned int sa_u32u __attribute__(( aligned( 1 )));
 
-template< int SRC > struct SAElem;
+template< int SRC > struct SAElem { typedef uint16_t T; }; // half 4, bf16 5
 template<> struct SAElem< 1 > { typedef uint8_t T; };
 template<> struct SAElem< 2 > { typedef uint16_t T; };
 template<> struct SAElem< 3 > { typedef float T; };
@@ -192,8 +192,8 @@ __device__ __forceinline__ void sa_dma4( const __amdgpu_buffer_rsrc_t rs,
 		: "memory" );
 }
 
-// SRC: 0 float RGBA by LDS-DMA; 1 uint8, 2 uint16, 3 float of CH channels
-// (lane = image row only). HOR (SRC 0): lanes are image rows -- a DMA
+// SRC: 0 float RGBA by LDS-DMA; 1 uint8, 2 uint16, 3 float, 4 half, 5 bfloat16
+// of CH channels (lane = image row only). HOR (SRC 0): image rows -- a DMA
 // instruction then fetches 16 rows x 4 consecutive samples (64 contiguous
 // bytes per row) instead of 64 rows x 1 sample: four times fewer cache lines
 // per instruction.
@@ -273,7 +273,7 @@ __global__ void __launch_bounds__( 64 ) k_sacc( const SAParams P )
 	};
 
 	// ---- the sample feed
-	constexpr int G = ( SRC == 1 ? 4 : ( SRC == 2 ? 2 : ( SRC == 0 ? 4 : 1 )));
+	constexpr int G = ( SRC == 1 ? 4 : sa_src2( SRC ) ? 2 : ( SRC == 0 ? 4 : 1 ));
 	typedef typename SAElem< SRC > :: T Tin;
 	// groups are aligned in absolute sample coordinates
 	const int ub0 = ( u_a >= 0 ? u_a / G : -(( -u_a + G - 1 ) / G )) * G;
@@ -396,10 +396,10 @@ __global__ void __launch_bounds__( 64 ) k_sacc( const SAParams P )
 							0xffu );
 					}
 					else
-					if( SRC == 2 )
+					if( sa_src2( SRC )) // (half, bfloat16: widened exactly)
 					{
-						v[ c ] = (float) (( gw[ ei >> 1 ] >> (( ei & 1 ) * 16 )) &
-							0xffffu );
+						v[ c ] = sa_elem< SRC >(( gw[ ei >> 1 ] >> (( ei & 1 ) *
+							16 )) & 0xffffu );
 					}
 					else
 					{
@@ -422,7 +422,7 @@ __global__ void __launch_bounds__( 64 ) k_sacc( const SAParams P )
 #pragma unroll
 				for( int c = 0; c < CH; c++ )
 				{
-					v[ c ] = (float) px[ c ];
+					v[ c ] = sa_elem< SRC >( px[ c ]);
 				}
 
 				f4 o; o.x = v[ 0 ]; o.y = v[ 1 ]; o.z = v[ 2 ]; o.w = v[ 3 ];
@@ -1053,7 +1053,7 @@ __device__ __forceinline__ void sa2_emit( SA2Acc< NC >& R, SAV< NC > ( &w )[ 8 ]
 }
 
 // SRC 1 / 2: uint8 / uint16 pixels of CH channels; lanes are image ROWS (the
-// caller's image: the first pass of a plan with an integer source)
+// caller's image: a plan's first pass). 4 / 5: half / bfloat16, optimistically
 template< int SRC, int CH, int NC >
 __global__ void __launch_bounds__( 64 ) k_sacc2( const SAParams P )
 {
@@ -1207,7 +1207,7 @@ __global__ void __launch_bounds__( 64 ) k_sacc2( const SAParams P )
 		{
 			const int ei = j * CH + c;
 
-			v[ c ] = (float) (( h_get( curA, ei / EPD ) >> (( ei % EPD ) *
+			v[ c ] = sa_elem< SRC >(( h_get( curA, ei / EPD ) >> (( ei % EPD ) *
 				( 32 / EPD ))) & ( SRC == 1 ? 0xffu : 0xffffu ));
 		}
 
@@ -2105,9 +2105,9 @@ static void sa_launch1( const SAParams& P, int ch, int items, size_t lds,
 }
 
 // One pass. src_type / src_ch: AVIRHIP_F32 with 4 channels goes by LDS-DMA
-// (16-byte aligned base and strides required: returns 1 otherwise); U8, U16
-// and narrower floats are read as they are, and only come as row lanes. Every
-// refusal (1) comes before the launch.
+// (16-byte aligned base and strides required: returns 1 otherwise); U8, U16,
+// F16, BF16 and narrower floats are read as they are, and only come as row
+// lanes (never with `out`). Every refusal (1) comes before the launch.
 int sacc_run_axis( const SAData* D, const SAPass& G, const SAForm& F,
 	hipStream_t st )
 {
@@ -2170,7 +2170,7 @@ int sacc_run_axis( const SAData* D, const SAPass& G, const SAForm& F,
 	// lanes read pixels of src_ch floats as they lie, s_step == src_ch * 4)
 	const bool two = ( F.finite && !F.ladder && D -> a.tab2 != nullptr &&
 		P.ax.in_len >= 8 && (( rows && out == nullptr &&
-		(( !dma && ( src_type == AVIRHIP_U8 || src_type == AVIRHIP_U16 )) ||
+		(( !dma && ( src_type == AVIRHIP_U8 || sa_type2( src_type ))) ||
 		( src_type == AVIRHIP_F32 && s_step == (long) src_ch * 4 &&
 		( (uintptr_t) src & 3 ) == 0 && ( s_lane & 3 ) == 0 &&
 		(double) s_lane * lane_hi < 2147483648.0 ))) ||
@@ -2295,8 +2295,20 @@ int sacc_run_axis( const SAData* D, const SAPass& G, const SAForm& F,
 			sa2_launch1< 1 >( P, src_ch, items, st );
 		}
 		else
+		if( src_type == AVIRHIP_U16 )
 		{
 			sa2_launch1< 2 >( P, src_ch, items, st );
+		}
+		else
+		if( src_type == AVIRHIP_F16 )
+		{
+			// (half, bfloat16: only ever optimistically, F.alarm_set -- the
+			// caller lowers the alarm, this kernel has no code for it)
+			sa2_launch1< 4 >( P, src_ch, items, st );
+		}
+		else
+		{
+			sa2_launch1< 5 >( P, src_ch, items, st );
 		}
 
 		AVIRHIP_HIPCHECK( hipGetLastError() );
@@ -2335,6 +2347,16 @@ int sacc_run_axis( const SAData* D, const SAPass& G, const SAForm& F,
 	if( src_type == AVIRHIP_F32 )
 	{
 		sa_launch1< 3 >( P, src_ch, items, lds, st );
+	}
+	else
+	if( src_type == AVIRHIP_F16 )
+	{
+		sa_launch1< 4 >( P, src_ch, items, lds, st );
+	}
+	else
+	if( src_type == AVIRHIP_BF16 )
+	{
+		sa_launch1< 5 >( P, src_ch, items, lds, st );
 	}
 	else
 	{

@@ -70,10 +70,14 @@ typedef enum avirhip_dtype {
  * the caller's images: CImageResizer's exact-2x marching kernel k_up2, its
  * whole-ratio (2x, 3x) downsizing kernel k_dnfh, and CLancIR's exact-2x kernel
  * k_lanc2h. At any other ratio CImageResizer's pass kernels do, for pixels of
- * 1-4 channels: k_gh reads a half source where it lies, and the last pass
- * -- k_gv, k_gf, the accumulation kernels k_sacc* -- narrows and stores a half
- * result; an axis that streams (k >= 2), k_gf and k_gh2 read the pack pass's
- * float copy of the source. CLancIR's pass kernels do the same at its other
+ * 1-4 channels: k_gh reads a half source where it lies, and so do the
+ * accumulation kernels k_sacc / k_sacc2 where the horizontal axis downsizes by
+ * 2 or more and the frame has 65,536 pixels or more (any row pitch, a base
+ * that is a multiple of 2); the last pass -- k_gv, k_gf, k_sacc* -- narrows
+ * and stores a half result; smaller frames of such an axis, k_gf and k_gh2
+ * read the pack pass's float copy of the source. From 3,600,000 source pixels
+ * on, such a downsizing call takes these kernels by itself, without a float
+ * copy of either image. CLancIR's pass kernels do the same at its other
  * ratios, 1-4 channels: k_lf (upsizing, one launch) and k_gv read a half
  * source where it lies -- dword-aligned base and row pitch, more than 48
  * columns, up to 24 taps -- and k_lf / k_gh apply the gain, narrow and store a
@@ -101,8 +105,9 @@ typedef enum avirhip_dtype {
 	 * refuse bfloat16 elements (AVIRHIP_EUNSUPPORTED) as they refuse half ones;
 	 * CLancIR accepts them on either side under the same rule. (k_up2, k_dnfh
  * and k_lanc2h read and store bfloat16 RGBA pixels themselves, as they do
- * half ones, and so do the pass kernels -- k_gh the source, k_gv / k_gf /
- * k_sacc* the result, 1-4 channels -- at every other ratio, and CLancIR's:
+ * half ones, and so do the pass kernels -- k_gh and k_sacc / k_sacc2 the
+ * source, k_gv / k_gf / k_sacc* the result, 1-4 channels, under the same
+ * conditions as for half -- at every other ratio, and CLancIR's:
  * k_lf / k_gv the source, k_lf / k_gh the result.) */
 	AVIRHIP_BF16 = 6
 } avirhip_dtype;

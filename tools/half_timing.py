@@ -50,10 +50,20 @@ k_gv + k_gh (AVIRHIP_VARIANT_UPG_TWO_PASS) with a half RGBA result at x1.5,
 x2.5, x3 and x4 from 1920x1080. With PARENT.so also README's CLancIR rows of
 uint8 / float32 images on both builds, alternating.
 
+--sacc measures downsizing by a non-integer ratio of 2 or more with 16-bit
+sources by the same method -- 5184x3456 -> 1920x1280 (RGBA and RGB), 3840x2160
+-> 1500x844, 1920x1080 -> 700x394, 640x480 -> 233x175, the mixed 3840x1080 ->
+1500x1400, half and bfloat16 -- as float32 on path 5; the 16-bit call on
+forced path 5 on the typed exact road (k_sacc< 4 / 5 >), the typed optimistic
+one (k_sacc2< 4 / 5 > first), the branch-free launches alone and the pack road
+(AVIRHIP_GP_NO_IO16); and the automatic path before and with path 5 admitted
+(AVIRHIP_SA16_AUTO_MINPIX). With PARENT.so also README's uint8 and float32
+accumulation rows on both builds, alternating.
+
 usage: python tools/half_timing.py [--bf16 | --lancir | --dnf | --gpass |
-       --lancgp] [PARENT.so] [REPS=5] [ONLY]
-(ONLY, with --gpass and --lancgp: the shapes whose names hold one of these
-comma-separated words, e.g. "u8")"""
+       --lancgp | --sacc] [PARENT.so] [REPS=5] [ONLY]
+(ONLY, with --gpass, --lancgp and --sacc: the shapes whose names hold one of
+these comma-separated words, e.g. "u8")"""
 import ctypes as C
 import hashlib
 import os
@@ -538,7 +548,162 @@ def lancgp_main(argv):
         torch.cuda.empty_cache()
 
 
+def sacc_main(argv):
+    """--sacc: downsizing by a non-integer ratio of 2 or more with 16-bit
+    sources (the accumulation kernels' typed loaders 4 / 5). Rows per shape and
+    type, all in this process and alternating: float32 on forced path 5; the
+    16-bit call on forced path 5 as the typed exact road, as the typed
+    optimistic road (AVIRHIP_VARIANT_SACC_OPTIMISTIC), with the branch-free
+    launches alone (AVIRHIP_SACC_OPT_ONLY) and on the pack road
+    (AVIRHIP_GP_NO_IO16); and the automatic path as built, as it chose before
+    the typed road (a plan made under AVIRHIP_SA16_AUTO_MINPIX = never) and
+    with path 5 admitted (= 0). With PARENT.so: README's uint8 and float32 accumulation
+    rows on both builds."""
+    import torch
+    import avir_amd
+    from avir_amd import abi, synth
+    parent = argv[1] if len(argv) > 1 and argv[1] != "-" else None
+    reps = int(argv[2]) if len(argv) > 2 else 5
+    only = argv[3].split(",") if len(argv) > 3 else None
+    lib = abi.load()
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    header(lib, parent)
+    F32, F16, BF16, U8 = abi.F32, abi.F16, abi.BF16, abi.U8
+    TD = {F32: torch.float32, F16: torch.float16, BF16: torch.bfloat16,
+          U8: torch.uint8}
+    ES = {F32: 4, F16: 2, BF16: 2, U8: 1}
+    NM = {F32: "f32", F16: "f16", BF16: "bf16", U8: "u8"}
+    NO = {"AVIRHIP_GP_NO_IO16": "1"}
+    ALONE = {"AVIRHIP_SACC_OPT_ONLY": "1"}
+    OPT = abi.VARIANT_SACC_OPTIMISTIC
+    NEVER = {"AVIRHIP_SA16_AUTO_MINPIX": str(1 << 60)}
+    ALWAYS = {"AVIRHIP_SA16_AUTO_MINPIX": "0"}
+
+    # a row: (tag, library, tin, tout, channels, forced path, variant,
+    #         environment of the plan's making, environment of the call)
+    def rows16(ti, to, ch=4, auto=True):
+        t = "%s->%s" % (NM[ti], NM[to]) + (" RGB" if ch == 3 else "")
+        # (AVIRHIP_VARIANT_SACC_LADDER: the exact kernels whatever the size)
+        r = [(t + " typed exact", lib, ti, to, ch, 5, abi.VARIANT_SACC_LADDER,
+              {}, {}),
+             (t + " typed optimistic", lib, ti, to, ch, 5, OPT, {}, {}),
+             (t + " branch-free alone", lib, ti, to, ch, 5, OPT, {}, ALONE),
+             (t + " pack road", lib, ti, to, ch, 5, 0, {}, NO)]
+        if auto:
+            r += [(t + " auto as built", lib, ti, to, ch, 0, 0, {}, {}),
+                  (t + " auto before", lib, ti, to, ch, 0, 0, NEVER, {}),
+                  (t + " auto, path 5 admitted", lib, ti, to, ch, 0, 0, ALWAYS,
+                   {})]
+        return r
+
+    def f32row(ch=4):
+        return [("f32->f32" + (" RGB" if ch == 3 else "") + " path 5", lib, F32,
+                 F32, ch, 5, 0, {}, {})]
+
+    shapes = [
+        ("5184 RGBA", (5184, 3456, 1920, 1280),
+         f32row() + rows16(F16, F16) + rows16(BF16, BF16)),
+        ("5184 RGB", (5184, 3456, 1920, 1280),
+         f32row(3) + rows16(F16, F16, 3) + rows16(BF16, BF16, 3)),
+        ("4K", (3840, 2160, 1500, 844),
+         f32row() + rows16(F16, F16) + rows16(BF16, BF16) +
+         rows16(F16, F16, 3)),
+        ("4K pairs", (3840, 2160, 1500, 844),
+         [("f32->f16 path 5", lib, F32, F16, 4, 5, 0, {}, {})] +
+         rows16(F16, F32, 4, False)),
+        ("1080p", (1920, 1080, 700, 394),
+         f32row() + rows16(F16, F16) + rows16(BF16, BF16) +
+         rows16(F16, F16, 3)),
+        ("480p", (640, 480, 233, 175),
+         f32row() + rows16(F16, F16) + rows16(BF16, BF16) +
+         rows16(F16, F16, 3)),
+        ("mixed", (3840, 1080, 1500, 1400),
+         f32row() + rows16(F16, F16, 4, False) + rows16(BF16, BF16, 4, False)),
+        # between the shapes above: where the automatic path and the
+        # optimistic form cross, and the smallest frames over the floor
+        ("1800p", (3200, 1800, 1200, 675),
+         rows16(F16, F16) + rows16(BF16, BF16) + rows16(F16, F16, 3)),
+        ("1440p", (2560, 1440, 1000, 563),
+         rows16(F16, F16) + rows16(BF16, BF16) + rows16(F16, F16, 3)),
+        ("240p", (320, 240, 117, 88),
+         rows16(F16, F16, 4, False) + rows16(BF16, BF16, 4, False) +
+         rows16(F16, F16, 3, False)),
+    ]
+    if parent:
+        P = abi.load_path(parent)
+        for name, g, ti, ch in (
+                ("parent 5184 RGB u8", (5184, 3456, 1920, 1280), U8, 3),
+                ("parent 5184 RGBA f32", (5184, 3456, 1920, 1280), F32, 4),
+                ("parent 4K RGBA f32", (3840, 2160, 1500, 844), F32, 4)):
+            shapes.append((name, g, [
+                ("this build", lib, ti, ti, ch, 0, 0, {}, {}),
+                ("parent build", P, ti, ti, ch, 0, 0, {}, {}),
+                ("this build again", lib, ti, ti, ch, 0, 0, {}, {})]))
+    for name, (sw, sh, nw, nh), rows in shapes:
+        if only is not None and not any(o in name for o in only):
+            continue
+        base = torch.from_numpy(synth.lcg_f32((sh, sw, 4))).to(dev)
+        run, keep, rings = {}, [], {}
+        for tag, L, ti, to, ch, path, variant, penv, env in rows:
+            pair = sw * sh * ch * ES[ti] + nw * nh * ch * ES[to]
+            n = max(2, -(-(512 << 20) // pair))
+            if (ti, to, ch) not in rings:  # (rows of a kind share their ring)
+                ring = []
+                for i in range(n):
+                    b = torch.roll(base, i, 0)[:, :, :ch]
+                    if ti == U8:
+                        b = b * 255.0
+                    s = b.contiguous().to(TD[ti])
+                    d = torch.empty((nh, nw, ch), dtype=TD[to], device=dev)
+                    ring.append((s, d))
+                rings[(ti, to, ch)] = ring
+            ring = rings[(ti, to, ch)]
+            with abi.using(L), _env(penv):
+                r = avir_amd.CImageResizer(8 if to == U8 else 16)
+                p = r.plan(sw, sh, nw, nh, ch, 0.0, None, ti, to)
+                abi.check(L.avirhip_plan_set_path(p, path), "set_path")
+                abi.check(L.avirhip_plan_set_variant(p, variant), "variant")
+            keep.append(r)
+
+            def once(L=L, p=p, ring=ring, env=env):
+                t = 0.0
+                ms = C.c_double()
+                with _env(env):
+                    for s, d in ring:
+                        abi.check(L.avirhip_time_resize(
+                            p, s.data_ptr(), d.data_ptr(), 1, st, C.byref(ms)),
+                            "time_resize")
+                        t += ms.value
+                return t / len(ring)
+            run[tag] = (once, pair, n, L, p)
+        for tag in run:  # warm-up, clocks
+            for _ in range(5):
+                run[tag][0]()
+        torch.cuda.synchronize()
+        res = {tag: [] for tag in run}
+        loops = 10
+        for _ in range(reps):
+            for tag in run:
+                res[tag].append(sum(run[tag][0]() for _ in range(loops)) / loops)
+        print("%s (%dx%d -> %dx%d), %d reps x %d ring passes:" % (
+            name, sw, sh, nw, nh, reps, loops))
+        for tag in run:
+            v = sorted(res[tag])
+            print("  %-36s %.4f ms  (min %.4f max %.4f)  path %d  ring %d  "
+                  "plan holds %.1f MB" % (
+                      tag, v[len(v) // 2], v[0], v[-1],
+                      run[tag][3].avirhip_plan_get_path(run[tag][4]),
+                      run[tag][2],
+                      run[tag][3].avirhip_plan_device_bytes(run[tag][4]) / 1e6),
+                  flush=True)
+        del keep, run, rings
+        torch.cuda.empty_cache()
+
+
 def main():
+    if "--sacc" in sys.argv:
+        return sacc_main([a for a in sys.argv if a != "--sacc"])
     if "--lancgp" in sys.argv:
         return lancgp_main([a for a in sys.argv if a != "--lancgp"])
     if "--gpass" in sys.argv:
