@@ -824,6 +824,18 @@ static bool fused_io()
 	return( on );
 }
 
+// The line of a stage a call steps aside to, under AVIRHIP_VERBOSE (read per
+// call, as the launchers' own lines): "pack pass" -- the float copy of the
+// caller's source; "output stage" -- the caller's pixels made from a float
+// result. tests/test_gpu_align.py reads the road a call took from them.
+static void verbose_stage( const char* const name, const int rows )
+{
+	if( getenv( "AVIRHIP_VERBOSE" ) != nullptr )
+	{
+		fprintf( stderr, "%s: %d rows\n", name, rows );
+	}
+}
+
 // ---- LANCIR ----
 
 // A LANCIR plan's own kernels, fastest first: the exact-2x marching kernel,
@@ -975,6 +987,7 @@ static int lancir_owner( avirhip_plan* p, const void* src, void* dst,
 			(size_t) p -> src_w * p -> src_h * 4 );
 
 		if( r != 0 ) return( r );
+		verbose_stage( "pack pass", sb - sa + 1 );
 
 		return( launch_pack( (const char*) src + (size_t) sa *
 			p -> src_stride * dtype_size( p -> in_type ), p -> in_type,
@@ -1024,6 +1037,7 @@ static int lancir_owner( avirhip_plan* p, const void* src, void* dst,
 
 			if( rc == 0 && !dst_own )
 			{
+				verbose_stage( "output stage", row1 - row0 );
 				rc = launch_lancir_out( p, p -> lres, (long) p -> new_w * 4, dst,
 					row1 - row0, st );
 			}
@@ -1080,6 +1094,8 @@ static int lancir_owner( avirhip_plan* p, const void* src, void* dst,
 		return( rc );
 	}
 
+	verbose_stage( "output stage", row1 - row0 );
+
 	if( p -> io_ch == 4 )
 	{
 		return( launch_lancir_out( p, p -> lres, (long) p -> new_w * 4, dst,
@@ -1134,6 +1150,7 @@ static int avir_pack( avirhip_plan* p, AvirSrc& S, int row0, int row1,
 	const char* const ps = (const char*) S.img + (size_t) pa *
 		p -> src_stride * dtype_size( p -> in_type );
 	float* const pd = p -> packed + (size_t) pa * p -> src_w * p -> ch;
+	verbose_stage( "pack pass", pb - pa + 1 );
 
 	if( p -> gamma )
 	{
@@ -1360,6 +1377,8 @@ static int avir_fast( avirhip_plan* p, const int path, AvirSrc& S, void* dst,
 static int avir_output( avirhip_plan* p, const float* fdst, void* dst,
 	int row0, int row1, hipStream_t st )
 {
+	verbose_stage( "output stage", row1 - row0 );
+
 	if( p -> dither == AVIRHIP_DITHER_ERRD )
 	{
 		// recursive ditherer: whole frames only (exec_any refuses bands).

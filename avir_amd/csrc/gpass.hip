@@ -2134,7 +2134,8 @@ int gpass_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 	{
 		// (half / bfloat16 pixels of 1-4 channels: narrowed in the store,
 		// gp_store_int_row; elements are stored whole, so the image is a
-		// multiple of their size)
+		// multiple of their size -- as gp_store_int stores uint16 elements,
+		// through an `unsigned short*`: an even address, up2_run's `io` 2)
 		const bool out16 = dtype_is_float16_kind( p -> out_type );
 
 		if( p -> is_lancir || p -> gamma ||
@@ -2144,6 +2145,7 @@ int gpass_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 			!( p -> out_type == AVIRHIP_F32 && p -> io_ch < 4 ) && !out16 ) ||
 			( p -> out_type == AVIRHIP_U8 && p -> io_ch == 4 &&
 			(( (uintptr_t) iout & 3 ) != 0 )) ||
+			( p -> out_type == AVIRHIP_U16 && ( (uintptr_t) iout & 1 ) != 0 ) ||
 			( out16 && ( !gpass_io16() || ( (uintptr_t) iout & 1 ) != 0 )))
 		{
 			return( 1 );

@@ -371,7 +371,23 @@ unsigned long long avirhip_plan_device_bytes(avirhip_plan* plan);
  * src -> dst. `src_mem`/`dst_mem` are AVIRHIP_MEM_HOST or _DEVICE; host
  * buffers are staged through device memory inside the call. `stream` is a
  * hipStream_t (NULL = default stream). With device buffers the call is
- * asynchronous with respect to the host. */
+ * asynchronous with respect to the host.
+ * Alignment of the images (this call, avirhip_resize_band and
+ * avirhip_resize_window alike): any base that is a multiple of the element
+ * size, and any source row pitch of at least src_w * channels elements, is
+ * served with the reference's bits on the automatic path, and nothing outside
+ * the destination's rows is written (CLancIR: nothing between them either).
+ * The fast kernels ask more -- 16-byte float RGBA rows, dword-aligned integer
+ * rows where they travel as bytes, a dword base for fused uint8 RGBA stores:
+ * DESIGN.md section 4e has the table, family by family, with the predicate
+ * that says so. A call that misses it steps aside to the pack pass, to a float
+ * result and the output stage, or to the generic kernels; a plan forced onto a
+ * path (avirhip_plan_set_path) whose kernel has no such stage refuses the call
+ * with AVIRHIP_EUNSUPPORTED and stores nothing. tests/test_gpu_align.py stands
+ * every kernel family on both sides of each of these. Bases that are no
+ * multiple of the element size are served where the half / bfloat16 suites
+ * pin that (the pack pass and the output stage take them); for the other
+ * element types no test stands there (tests/align_cases.py: LEFT_OUT). */
 int avirhip_resize(avirhip_plan* plan, const void* src, int src_mem,
 	void* dst, int dst_mem, void* stream);
 

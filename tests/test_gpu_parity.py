@@ -2001,7 +2001,10 @@ def test_misaligned_device_buffers():
                     a = synth.lcg_f32((sh, sw, ch), seed=5)
                 es = a.dtype.itemsize
                 r = avir_amd.CLancIR() if lanc else avir_amd.CImageResizer(8 if es == 1 else 16)
-                want = r.resize(a, nw, nh)
+                # (the reference's bits, not the library's own host call)
+                want = (_checker_lancir(a, nw, nh) if lanc else
+                        _checker_avir(a, nw, nh, resbits=8 if es == 1 else 16))
+                assert want.shape == (nh, nw, ch) and want.dtype == a.dtype
                 n_in, n_out = a.size, nh * nw * ch
                 for off_in, off_out in [(0, 0), (1, 0), (0, 1), (3, 2), (2, 3)]:
                     tin = torch.zeros(n_in + 8, dtype=torch.from_numpy(a).dtype, device=dev)
