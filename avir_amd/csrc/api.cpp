@@ -1409,6 +1409,75 @@ static int avir_output( avirhip_plan* p, const float* fdst, void* dst,
 		p -> d_gthr, ( p -> dither == AVIRHIP_DITHER_DEF_RNE )));
 }
 
+// Whole-ratio downsizing on both axes (path 2) WITH sRGB gamma and 8-bit pixels
+// on a side: k_dnfh's DH_S8 kinds -- one launch that linearises a uint8 RGBA
+// source where it lies (the plan's table) and de-linearises and stores a uint8
+// result itself (the plan's thresholds; the default ditherer). The sides are
+// independent: `s8` / `o8` say which of them the kernel may take.
+// AVIRHIP_VARIANT_DN_UNFUSED_IO: today's road (pack pass, k_dnf, output stage).
+//
+// The store side ALONE (a source the kernel cannot read: the pack pass in
+// front of k_dnfh< F32, S8 >) saves the output stage's launch and the float
+// result, and pays for the threshold search in the column waves, which the
+// DMA-fed row waves no longer hide: it is taken for frames of up to
+// dnsrgb_store_maxpix() source pixels (AVIRHIP_DNSRGB_STORE_MAXPIX, read per
+// call; measured in NOTEBOOK section 29).
+static long dnsrgb_store_maxpix()
+{
+	const char* const e = getenv( "AVIRHIP_DNSRGB_STORE_MAXPIX" );
+
+	return( e != nullptr ? atol( e ) : 1000000L );
+}
+
+static bool avir_dnsrgb( const avirhip_plan* p, const int path, bool& s8,
+	bool& o8 )
+{
+	s8 = ( p -> in_type == AVIRHIP_U8 && p -> io_ch == 4 );
+	o8 = ( p -> out_type == AVIRHIP_U8 && p -> dither == AVIRHIP_DITHER_DEF &&
+		p -> d_gthr != nullptr );
+
+	return( path == 2 && p -> gamma && !p -> fp4 && !p -> f64 && p -> ch == 4 &&
+		fused_io() && !( p -> variant & AVIRHIP_VARIANT_DN_UNFUSED_IO ) &&
+		( s8 || o8 ) && fused_dn16( p ));
+}
+
+// The call of that road. A source the kernel refuses (a base or a pitch that
+// is no multiple of 4 bytes) or cannot read (RGB, uint16, float) goes through
+// the pack pass's linear copy; a result it cannot store goes as linear float
+// rows to `fdst` (the caller's float RGBA image, or `resbuf` and the output
+// stage). Returns 1 when neither side is the kernel's after all, or its
+// launcher refuses: today's road; 0: `stored` as avir_fast's.
+static int avir_dnsrgb_run( avirhip_plan* p, const bool s8, const bool o8,
+	AvirSrc& S, void* dst, float*& fdst, const bool direct, int row0, int row1,
+	hipStream_t st, bool& stored )
+{
+	int rc;
+	const bool src_own = ( s8 && ( (uintptr_t) S.img & 3 ) == 0 &&
+		( p -> src_stride & 3 ) == 0 );
+
+	stored = false;
+
+	if( !src_own && ( !o8 ||
+		(long) p -> src_w * p -> src_h > dnsrgb_store_maxpix() ))
+	{
+		return( 1 );
+	}
+
+	if( !src_own && ( rc = avir_pack( p, S, row0, row1, st )) != 0 )
+		return( rc );
+
+	if( !o8 && ( rc = avir_need_res( p, fdst, direct )) != 0 ) return( rc );
+
+	const ImageRef hsrc = ( src_own ? ImageRef{ S.img, AVIRHIP_U8, 4,
+		p -> src_stride } : ImageRef{ S.f, AVIRHIP_F32, 4, S.fstride });
+
+	rc = fused_run_dnsrgb( p, hsrc, fdst, row0, row1, st,
+		( o8 ? dst : nullptr ));
+
+	stored = ( rc == 0 && o8 );
+	return( rc );
+}
+
 static int exec_avir( avirhip_plan* p, const void* src, void* dst, int row0,
 	int row1, hipStream_t st, const SrcWindow win )
 {
@@ -1420,7 +1489,10 @@ static int exec_avir( avirhip_plan* p, const void* src, void* dst, int row0,
 	const bool gp16 = ( path == 5 && !p -> gamma && gpass_io16() &&
 		( dtype_is_float16_kind( p -> in_type ) ||
 		dtype_is_float16_kind( p -> out_type )));
-	int rc = ( avir_dn16( p, path ) || gp16 ? AVIRHIP_OK :
+	// (nor does k_dnfh's road with gamma: avir_dnsrgb)
+	bool s8, o8;
+	const bool srgb = avir_dnsrgb( p, path, s8, o8 );
+	int rc = ( avir_dn16( p, path ) || gp16 || srgb ? AVIRHIP_OK :
 		ensure_scratch( p ));
 	if( rc != 0 ) return( rc );
 
@@ -1438,6 +1510,34 @@ static int exec_avir( avirhip_plan* p, const void* src, void* dst, int row0,
 	const bool direct = ( p -> out_type == AVIRHIP_F32 &&
 		p -> ch == p -> io_ch && !( p -> fp4 && p -> gamma ));
 	float* fdst = ( direct ? (float*) dst : p -> resbuf );
+
+	if( srgb )
+	{
+		bool stored = false;
+		rc = avir_dnsrgb_run( p, s8, o8, S, dst, fdst, direct, row0, row1, st,
+			stored );
+
+		if( rc == 0 )
+		{
+			return( stored || direct ? AVIRHIP_OK :
+				avir_output( p, fdst, dst, row0, row1, st ));
+		}
+
+		if( rc != 1 )
+		{
+			return( rc );
+		}
+
+		// today's road, with the float copies it expects to find
+		if(( rc = ensure_scratch( p )) != 0 ) return( rc );
+
+		if( need_pack )
+		{
+			S.f = p -> packed;
+		}
+
+		fdst = ( direct ? (float*) dst : p -> resbuf );
+	}
 
 	rc = 1;
 

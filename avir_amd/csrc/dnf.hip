@@ -52,7 +52,7 @@
 #include <stdlib.h>
 #include <stdio.h>
 #include <vector>
-
+#include "dnsrgb_dev.h"
 namespace avirhip {
 
 #define DF_W 42     // output columns per strip
@@ -864,9 +864,92 @@ int dn_run_hv( void* d, const float* src, long src_ss, float* dst, int row0,
 //        DH_F32: k_dnf's stores (float RGBA rows, or df_store_elem).
 // Float on both sides is k_dnf's own and is not instantiated. The timing
 // ablations of AVIRHIP_DNF_DBG are k_dnf's alone.
-enum { DH_F32 = 0, DH_F16 = 1, DH_BF16 = 2 };
+//
+// With sRGB gamma (DnSParams; dnsrgb_dev.h has the stages' expressions):
+//   SRC  DH_S8: the caller's uint8 RGBA rows. ONE 4-byte buffer load per
+//        pixel, issued a step ahead like the 8-byte ones; at the head of the
+//        step the lane linearises it -- tbl[ v ] per colour channel from an
+//        LDS copy of the plan's 256-entry table, (float) v * gm for the alpha
+//        channel -- and writes the slot of sS: the pack pass's float pixel.
+//   OUT  DH_S8: a uint8 result of 1-4 channels. A column wave's lane counts
+//        the thresholds <= its value (k_epilogue_gamma_thr's eight compares
+//        over an LDS copy of the plan's 2 x 256 thresholds; the step's 6 or 8
+//        outputs are searched level by level, so a level's LDS reads are
+//        independent of each other) and stores one byte at x * ch + c.
+//        Values outside |v| <= 16 take that kernel's direct expression.
+//   A workgroup fills its tables once, before its first step, behind a
+//   barrier of their own. Pairs: (S8, S8), (S8, F32), (F32, S8).
+enum { DH_F32 = 0, DH_F16 = 1, DH_BF16 = 2, DH_S8 = 3 };
+
+// DnFParams and the gamma stages' parameters: the kernels with a DH_S8 side
+struct DnSParams
+{
+	DnFParams F;
+	DnGamma G;
+};
+
+__device__ __forceinline__ const DnFParams& dh_core( const DnFParams& p )
+{
+	return( p );
+}
+
+__device__ __forceinline__ const DnFParams& dh_core( const DnSParams& p )
+{
+	return( p.F );
+}
+
+template< int SRC, int OUT >
+struct DhParams
+{
+	typedef DnFParams type;
+};
+
+template< int OUT >
+struct DhParams< DH_S8, OUT >
+{
+	typedef DnSParams type;
+};
+
+template<>
+struct DhParams< DH_F32, DH_S8 >
+{
+	typedef DnSParams type;
+};
 
 typedef unsigned int dh_u2 __attribute__(( ext_vector_type( 2 )));
+
+// a lane's uint8 RGBA pixel of one piece: dh_ld8's addressing and discipline
+__device__ __forceinline__ void dh_ld4( unsigned int& r,
+	const __amdgpu_buffer_rsrc_t rs, const int voff, const unsigned soff )
+{
+	asm volatile( "buffer_load_dword %0, %1, %2, %3 offen"
+		: "+v"( r ) : "v"( voff ), "s"( rs ), "s"( soff ) : "memory" );
+}
+
+// the pack pass's float pixel of a uint8 RGBA pixel (k_pack_gamma_px< uint8_t,
+// 4 >): `tbl` the LDS copy of the table, `ai` the alpha channel (0, 3, or
+// neither)
+__device__ __forceinline__ f4 dh_linear( const unsigned int w,
+	const float* const tbl, const int ai, const float gm )
+{
+	f4 v;
+	v.x = tbl[ w & 255u ];
+	v.y = tbl[ ( w >> 8 ) & 255u ];
+	v.z = tbl[ ( w >> 16 ) & 255u ];
+	v.w = tbl[ w >> 24 ];
+
+	if( ai == 0 )
+	{
+		v.x = (float) ( w & 255u ) * gm;
+	}
+
+	if( ai == 3 )
+	{
+		v.w = (float) ( w >> 24 ) * gm;
+	}
+
+	return( v );
+}
 
 // a lane's pixel of one piece: 8 bytes at voff + soff (gp_dma's addressing),
 // into registers the caller waits for (AVIRHIP_WAITCNT_VM) before it reads
@@ -950,10 +1033,91 @@ __device__ __forceinline__ void dh_wait_raw( dh_u2 ( &r )[ 2 ][ NP ])
 	}
 }
 
+template< int NP >
+__device__ __forceinline__ void dh_wait_raw( unsigned int ( &r )[ 2 ][ NP ])
+{
+	static_assert( NP == 2 || NP == 3, "pieces per row" );
+
+	if constexpr( NP == 3 )
+	{
+		asm volatile( AVIRHIP_WAITCNT_VM( 0 )
+			: "+v"( r[ 0 ][ 0 ]), "+v"( r[ 0 ][ 1 ]), "+v"( r[ 0 ][ 2 ]),
+			"+v"( r[ 1 ][ 0 ]), "+v"( r[ 1 ][ 1 ]), "+v"( r[ 1 ][ 2 ])
+			:: "memory" );
+	}
+	else
+	{
+		asm volatile( AVIRHIP_WAITCNT_VM( 0 )
+			: "+v"( r[ 0 ][ 0 ]), "+v"( r[ 0 ][ 1 ]), "+v"( r[ 1 ][ 0 ]),
+			"+v"( r[ 1 ][ 1 ]) :: "memory" );
+	}
+}
+
+// the level-by-level threshold search of a column wave's step: N values, each
+// the count of thresholds t[ 1 .. 255 ] <= v (k_epilogue_gamma_thr's compares)
+template< int N >
+__device__ __forceinline__ void dh_count( int ( &lo )[ N ],
+	const float ( &v )[ N ], const float* const t )
+{
+#pragma unroll
+	for( int k = 0; k < N; k++ )
+	{
+		lo[ k ] = 0;
+	}
+
+#pragma unroll
+	for( int s = 128; s >= 1; s >>= 1 )
+	{
+		float th[ N ];
+#pragma unroll
+		for( int k = 0; k < N; k++ )
+		{
+			th[ k ] = t[ lo[ k ] + s ];
+		}
+
+#pragma unroll
+		for( int k = 0; k < N; k++ )
+		{
+			lo[ k ] += ( v[ k ] >= th[ k ] ? s : 0 );
+		}
+	}
+}
+
+// a workgroup's LDS copies of the plan's tables: threads 0-255 the
+// linearising table (a DH_S8 source), threads 256-767 the thresholds (a DH_S8
+// result); the caller's barrier hands them over
+template< int SRC, int OUT >
+__device__ __forceinline__ void dh_fill_tables( const DnGamma& G,
+	const int tid )
+{
+	static_assert( DF_NTHR == 768, "one table element per thread" );
+
+	if constexpr( SRC == DH_S8 )
+	{
+		if( tid < 256 )
+		{
+			ds_table< 256 >()[ tid ] = G.tbl[ tid ];
+		}
+	}
+
+	if constexpr( OUT == DH_S8 )
+	{
+		if( tid >= 256 )
+		{
+			ds_table< 512 >()[ tid - 256 ] = G.thr[ tid - 256 ];
+		}
+	}
+}
+
 template< int KH, int NTH, int KV, int NTV, int DF_NHW, int SRC, int OUT >
-__global__ void __launch_bounds__( DF_NTHR ) k_dnfh( const DnFParams P )
+__global__ void __launch_bounds__( DF_NTHR ) k_dnfh(
+	const typename DhParams< SRC, OUT >::type PA )
 {
 	static_assert( SRC != DH_F32 || OUT != DH_F32, "float -> float is k_dnf" );
+	constexpr bool S8 = ( SRC == DH_S8 || OUT == DH_S8 );
+	static_assert( !S8 || (( SRC == DH_S8 || SRC == DH_F32 ) &&
+		( OUT == DH_S8 || OUT == DH_F32 )), "gamma: uint8 and float sides" );
+	const DnFParams& P = dh_core( PA );
 	constexpr int DF_NVW = 12 - DF_NHW;         // column waves
 	constexpr int DF_RS = 2 * DF_NHW;           // source rows per step
 	constexpr int DF_LPV = DF_W * 4 / DF_NVW;   // elements per column wave
@@ -1038,14 +1202,14 @@ __global__ void __launch_bounds__( DF_NTHR ) k_dnfh( const DnFParams P )
 		{
 			const int px = ( KH == 2 ? lane * 2 + q : q * 64 + lane );
 			voff[ q ] = dn_clampi( in0 + px, P.H.in_len - 1 ) *
-				( SRC == DH_F32 ? 16 : 8 );
+				( SRC == DH_F32 ? 16 : ( SRC == DH_S8 ? 4 : 8 ));
 		}
 
 		const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
 			(void*) P.src, 0, 0x7fffffff, 0x00020000 );
 
 		const unsigned row_b = (unsigned) P.src_ss *
-			( SRC == DH_F32 ? 4u : 2u );
+			( SRC == DH_F32 ? 4u : ( SRC == DH_S8 ? 1u : 2u ));
 		const unsigned lds_s = (unsigned) (unsigned long) (lds_char*)
 			&sS[ h ][ 0 ][ 0 ][ 0 ];
 
@@ -1055,15 +1219,18 @@ __global__ void __launch_bounds__( DF_NTHR ) k_dnfh( const DnFParams P )
 
 		const int vin_last = P.V.in_len - 1;
 
-		// a 16-bit source: the lane's pixels of the step ahead, as loaded
-		dh_u2 raw[ 2 ][ NPH ];
+		// a 16-bit or uint8 source: the lane's pixels of the step ahead, as
+		// loaded
+		typedef typename std::conditional< SRC == DH_S8, unsigned int,
+			dh_u2 >::type raw_t;
+		raw_t raw[ 2 ][ NPH ];
 #pragma unroll
 		for( int rr = 0; rr < 2; rr++ )
 		{
 #pragma unroll
 			for( int q = 0; q < NPH; q++ )
 			{
-				raw[ rr ][ q ] = (dh_u2) 0u;
+				raw[ rr ][ q ] = (raw_t) 0u;
 			}
 		}
 
@@ -1088,6 +1255,11 @@ __global__ void __launch_bounds__( DF_NTHR ) k_dnfh( const DnFParams P )
 							q * 64 ) * 16, voff[ q ], soff );
 					}
 					else
+					if constexpr( SRC == DH_S8 )
+					{
+						dh_ld4( raw[ rr ][ q ], rsrc, voff[ q ], soff );
+					}
+					else
 					{
 						dh_ld8( raw[ rr ][ q ], rsrc, voff[ q ], soff );
 					}
@@ -1096,6 +1268,14 @@ __global__ void __launch_bounds__( DF_NTHR ) k_dnfh( const DnFParams P )
 		};
 
 		issue( 0 );
+
+		// (the tables, behind the first step's loads: every wave of the
+		// workgroup fills its share, one barrier hands them over)
+		if constexpr( S8 )
+		{
+			dh_fill_tables< SRC, OUT >( PA.G, tid );
+			__syncthreads();
+		}
 
 		for( int s = 0; s < S; s++ )
 		{
@@ -1131,10 +1311,21 @@ __global__ void __launch_bounds__( DF_NTHR ) k_dnfh( const DnFParams P )
 #pragma unroll
 				for( int q = 0; q < NPH; q++ )
 				{
-					dh_st16< 0 >( wad + q * 1024,
-						dh_widen< SRC >( raw[ 0 ][ q ]));
-					dh_st16< ROWPX * 16 >( wad + q * 1024,
-						dh_widen< SRC >( raw[ 1 ][ q ]));
+					if constexpr( SRC == DH_S8 )
+					{
+						const float* const tb = ds_table< 256 >();
+						dh_st16< 0 >( wad + q * 1024, dh_linear( raw[ 0 ][ q ],
+							tb, PA.G.alpha_index, PA.G.gm ));
+						dh_st16< ROWPX * 16 >( wad + q * 1024, dh_linear(
+							raw[ 1 ][ q ], tb, PA.G.alpha_index, PA.G.gm ));
+					}
+					else
+					{
+						dh_st16< 0 >( wad + q * 1024,
+							dh_widen< SRC >( raw[ 0 ][ q ]));
+						dh_st16< ROWPX * 16 >( wad + q * 1024,
+							dh_widen< SRC >( raw[ 1 ][ q ]));
+					}
 				}
 
 				if( s + 1 < S )
@@ -1268,7 +1459,8 @@ __global__ void __launch_bounds__( DF_NTHR ) k_dnfh( const DnFParams P )
 
 		if( P.out.on != 0 )
 		{
-			const int es = ( OUT != DH_F32 ? 2 : P.out.type == AVIRHIP_U8 ? 1 :
+			const int es = ( OUT == DH_S8 ? 1 : OUT != DH_F32 ? 2 :
+				P.out.type == AVIRHIP_U8 ? 1 :
 				( P.out.type == AVIRHIP_U16 ? 2 : 4 ));
 
 			drs = __builtin_amdgcn_make_buffer_rsrc( P.out.base, 0,
@@ -1292,6 +1484,27 @@ __global__ void __launch_bounds__( DF_NTHR ) k_dnfh( const DnFParams P )
 			wr[ i ] = 0.0f;
 		}
 
+		// a uint8 result under gamma: the step's outputs (one every KV rows)
+		// wait here for the searches and stores at the end of the step; the
+		// thresholds of the lane's channel (the colour or the alpha half)
+		constexpr int NGO = DF_RS / KV;
+		float gv[ NGO ];
+		int gyr[ NGO ];
+		bool g_alpha = false;
+		const float* gthr = nullptr;
+
+		if constexpr( S8 )
+		{
+			dh_fill_tables< SRC, OUT >( PA.G, tid );
+			__syncthreads();
+		}
+
+		if constexpr( OUT == DH_S8 )
+		{
+			g_alpha = ( ch == PA.G.alpha_index );
+			gthr = ds_table< 512 >() + ( g_alpha ? 256 : 0 );
+		}
+
 		int s = 0;
 		int jl_base = 0; // local index of the output in slot 0 of this period
 
@@ -1304,6 +1517,16 @@ __global__ void __launch_bounds__( DF_NTHR ) k_dnfh( const DnFParams P )
 				if( s < S )
 				{
 					__syncthreads();
+
+					if constexpr( OUT == DH_S8 )
+					{
+#pragma unroll
+						for( int k = 0; k < NGO; k++ )
+						{
+							gv[ k ] = 0.0f;
+							gyr[ k ] = -1;
+						}
+					}
 					f2 vp[ DF_RS / 2 ];
 #pragma unroll
 					for( int m = 0; m < DF_RS / 2; m++ )
@@ -1388,6 +1611,14 @@ __global__ void __launch_bounds__( DF_NTHR ) k_dnfh( const DnFParams P )
 
 									const int yr = y - P.dst_row0;
 
+									if constexpr( OUT == DH_S8 )
+									{
+										// (outputs complete every KV rows:
+										// the step's i / KV-th)
+										gv[ i / KV ] = a;
+										gyr[ i / KV ] = yr;
+									}
+									else
 									if constexpr( OUT != DH_F32 )
 									{
 										__builtin_amdgcn_raw_buffer_store_b16(
@@ -1412,6 +1643,55 @@ __global__ void __launch_bounds__( DF_NTHR ) k_dnfh( const DnFParams P )
 						}
 					} );
 
+					if constexpr( OUT == DH_S8 )
+					{
+						int lo[ NGO ];
+						dh_count< NGO >( lo, gv, gthr );
+
+						// outside the range the thresholds were searched in the
+						// direct expression decides (dnsrgb_dev.h). Nothing an
+						// image holds: ONE copy of it per step, a loop over
+						// the lane's such values
+						unsigned int far = 0u;
+#pragma unroll
+						for( int k = 0; k < NGO; k++ )
+						{
+							far |= ( !( fabsf( gv[ k ]) <= 16.0f ) ? 1u << k :
+								0u );
+						}
+
+#pragma nounroll
+						while( far != 0u )
+						{
+							const int kf = __builtin_ctz( far );
+							far &= far - 1u;
+							float v = gv[ 0 ];
+#pragma unroll
+							for( int k = 1; k < NGO; k++ )
+							{
+								v = ( kf == k ? gv[ k ] : v );
+							}
+
+							const int bt = ds_direct_byte( v, g_alpha, PA.G );
+#pragma unroll
+							for( int k = 0; k < NGO; k++ )
+							{
+								lo[ k ] = ( kf == k ? bt : lo[ k ]);
+							}
+						}
+
+#pragma unroll
+						for( int k = 0; k < NGO; k++ )
+						{
+							if( gyr[ k ] >= 0 )
+							{
+								__builtin_amdgcn_raw_buffer_store_b8(
+									(unsigned char) lo[ k ], drs, st_voff,
+									gyr[ k ] * (int) P.out.stride, 0 );
+							}
+						}
+					}
+
 					s++;
 				}
 			} );
@@ -1428,23 +1708,53 @@ static int dh_kind( const int type )
 		( type == AVIRHIP_BF16 ? DH_BF16 : DH_F32 ));
 }
 
-// dn_run_hv with half / bfloat16 pixels on a side: RGBA source rows of `src`
-// (half, bfloat16 or float, read where they lie) -> destination rows
-// [row0, row1): float RGBA rows at `dst` (out == nullptr), or through `out` --
-// half / bfloat16 elements narrowed in the store, or the integer output stage.
+// The launcher of k_dnfh: RGBA source rows of `src`, read where they lie ->
+// destination rows [row0, row1): float RGBA rows at `dst` (out == nullptr), or
+// through `out`.
+//   G == nullptr  half, bfloat16 or float rows; half / bfloat16 elements
+//                 narrowed in the store, or the integer output stage
+//   G != nullptr  sRGB gamma: uint8 or float rows (the pack pass's linear copy);
+//                 a uint8 result of 1-4 channels de-linearised and stored
+//                 bytewise, or float rows (linear)
 // Returns 1 when the call is not this kernel's: float on both sides (k_dnf's),
-// an image lanc2h_image_ok refuses, rows beyond a 32-bit byte offset.
-int dn_run_hv16( void* d, const ImageRef& src, float* dst, int row0, int row1,
-	hipStream_t st, const GPOut* out )
+// a 16-bit image lanc2h_image_ok refuses, a uint8 source whose base or pitch is
+// no multiple of 4 bytes, rows beyond a 32-bit byte offset.
+static int dh_run( void* d, const ImageRef& src, float* dst, int row0, int row1,
+	hipStream_t st, const GPOut* out, const DnGamma* G )
 {
 	const DnData* D = (const DnData*) d;
-	const int sk = dh_kind( src.type );
-	const int ok = ( out != nullptr ? dh_kind( out -> type ) : DH_F32 );
+	int sk, ok;
+
+	if( G != nullptr )
+	{
+		sk = ( src.type == AVIRHIP_U8 ? DH_S8 : DH_F32 );
+		ok = ( out != nullptr ? DH_S8 : DH_F32 );
+
+		if(( sk == DH_F32 && src.type != AVIRHIP_F32 ) ||
+			( out != nullptr && ( out -> type != AVIRHIP_U8 || out -> ch < 1 ||
+			out -> ch > 4 || G -> thr == nullptr )) ||
+			( sk == DH_S8 && ( G -> tbl == nullptr ||
+			( (uintptr_t) src.ptr & 3 ) != 0 || ( src.stride & 3 ) != 0 )) ||
+			( sk == DH_F32 && (( (uintptr_t) src.ptr & 15 ) != 0 ||
+			( src.stride & 3 ) != 0 )))
+		{
+			return( 1 );
+		}
+	}
+	else
+	{
+		sk = dh_kind( src.type );
+		ok = ( out != nullptr ? dh_kind( out -> type ) : DH_F32 );
+
+		if( !lanc2h_image_ok( src.ptr, src.type, src.stride ) ||
+			( ok != DH_F32 && ( (uintptr_t) out -> base & 1 ) != 0 ))
+		{
+			return( 1 );
+		}
+	}
 
 	if( D == nullptr || !D -> hok || !D -> vok || src.ch != 4 ||
 		( sk == DH_F32 && ok == DH_F32 ) ||
-		!lanc2h_image_ok( src.ptr, src.type, src.stride ) ||
-		( ok != DH_F32 && ( (uintptr_t) out -> base & 1 ) != 0 ) ||
 		( out == nullptr && ( dst == nullptr || ( (uintptr_t) dst & 15 ) != 0 )))
 	{
 		return( 1 );
@@ -1455,27 +1765,36 @@ int dn_run_hv16( void* d, const ImageRef& src, float* dst, int row0, int row1,
 		return( AVIRHIP_OK );
 	}
 
-	// (row offsets of the loads and of the 16-bit stores are 32-bit, in bytes)
-	const long spb = src.stride * ( sk == DH_F32 ? 4L : 2L );
+	// (row offsets of the loads and of the 8- and 16-bit stores are 32-bit, in
+	// bytes)
+	const long spb = src.stride * ( sk == DH_F32 ? 4L : ( sk == DH_S8 ? 1L :
+		2L ));
 
 	if( (long) D -> v.in_len * spb >= 0x7fffffffL ||
-		( ok != DH_F32 && (long) ( row1 - row0 ) * out -> stride * 2 >=
-		0x7fffffffL ))
+		( ok != DH_F32 && (long) ( row1 - row0 ) * out -> stride *
+		( ok == DH_S8 ? 1 : 2 ) >= 0x7fffffffL ))
 	{
 		return( 1 );
 	}
 
-	DnFParams P;
+	DnSParams PS;
+	DnFParams& P = PS.F;
 	P.H = dnf_axis( D -> h );
 	P.V = dnf_axis( D -> v );
 	P.src = (const float*) src.ptr; P.src_ss = src.stride; // (elements)
 	P.dst = dst; P.dst_ss = (long) D -> h.out_len * 4; P.dst_row0 = row0;
 	P.row_lo = row0; P.row_hi = row1;
 	memset( &P.out, 0, sizeof( P.out ));
+	memset( &PS.G, 0, sizeof( PS.G ));
 
 	if( out != nullptr )
 	{
 		P.out = *out;
+	}
+
+	if( G != nullptr )
+	{
+		PS.G = *G;
 	}
 
 	P.dbg = 0;
@@ -1490,18 +1809,24 @@ int dn_run_hv16( void* d, const ImageRef& src, float* dst, int row0, int row1,
 
 #define DH_LAUNCH( SK, OK ) hipLaunchKernelGGL(( k_dnfh< KH, NTH, KV, NTV, NHW, \
 	SK, OK > ), grid, dim3( DF_NTHR ), 0, st, P )
+#define DH_LAUNCH8( SK, OK ) hipLaunchKernelGGL(( k_dnfh< KH, NTH, KV, NTV, NHW, \
+	SK, OK > ), grid, dim3( DF_NTHR ), 0, st, PS )
 #define DH_FORM( KH_, NTH_, KV_, NTV_, NHW_ ) do { \
 	constexpr int KH = KH_, NTH = NTH_, KV = KV_, NTV = NTV_, NHW = NHW_; \
-	switch( sk * 3 + ok ) \
+	switch( sk * 4 + ok ) \
 	{ \
-		case DH_F32 * 3 + DH_F16: DH_LAUNCH( DH_F32, DH_F16 ); break; \
-		case DH_F32 * 3 + DH_BF16: DH_LAUNCH( DH_F32, DH_BF16 ); break; \
-		case DH_F16 * 3 + DH_F32: DH_LAUNCH( DH_F16, DH_F32 ); break; \
-		case DH_F16 * 3 + DH_F16: DH_LAUNCH( DH_F16, DH_F16 ); break; \
-		case DH_F16 * 3 + DH_BF16: DH_LAUNCH( DH_F16, DH_BF16 ); break; \
-		case DH_BF16 * 3 + DH_F32: DH_LAUNCH( DH_BF16, DH_F32 ); break; \
-		case DH_BF16 * 3 + DH_F16: DH_LAUNCH( DH_BF16, DH_F16 ); break; \
-		default: DH_LAUNCH( DH_BF16, DH_BF16 ); break; \
+		case DH_F32 * 4 + DH_F16: DH_LAUNCH( DH_F32, DH_F16 ); break; \
+		case DH_F32 * 4 + DH_BF16: DH_LAUNCH( DH_F32, DH_BF16 ); break; \
+		case DH_F16 * 4 + DH_F32: DH_LAUNCH( DH_F16, DH_F32 ); break; \
+		case DH_F16 * 4 + DH_F16: DH_LAUNCH( DH_F16, DH_F16 ); break; \
+		case DH_F16 * 4 + DH_BF16: DH_LAUNCH( DH_F16, DH_BF16 ); break; \
+		case DH_BF16 * 4 + DH_F32: DH_LAUNCH( DH_BF16, DH_F32 ); break; \
+		case DH_BF16 * 4 + DH_F16: DH_LAUNCH( DH_BF16, DH_F16 ); break; \
+		case DH_BF16 * 4 + DH_BF16: DH_LAUNCH( DH_BF16, DH_BF16 ); break; \
+		case DH_S8 * 4 + DH_S8: DH_LAUNCH8( DH_S8, DH_S8 ); break; \
+		case DH_S8 * 4 + DH_F32: DH_LAUNCH8( DH_S8, DH_F32 ); break; \
+		case DH_F32 * 4 + DH_S8: DH_LAUNCH8( DH_F32, DH_S8 ); break; \
+		default: return( 1 ); \
 	} } while( 0 )
 
 	// (K = 3 along y: the 9 + 3 split, k_dnf's default)
@@ -1515,11 +1840,26 @@ int dn_run_hv16( void* d, const ImageRef& src, float* dst, int row0, int row1,
 	}
 
 #undef DH_FORM
+#undef DH_LAUNCH8
 #undef DH_LAUNCH
 	dnf_verbose( "k_dnfh", P.nstrips, P.nchunks, P.crows );
 
 	AVIRHIP_HIPCHECK( hipGetLastError() );
 	return( AVIRHIP_OK );
+}
+
+// dn_run_hv with half / bfloat16 pixels on a side
+int dn_run_hv16( void* d, const ImageRef& src, float* dst, int row0, int row1,
+	hipStream_t st, const GPOut* out )
+{
+	return( dh_run( d, src, dst, row0, row1, st, out, nullptr ));
+}
+
+// ... with sRGB gamma and 8-bit pixels on a side
+int dn_run_hv8( void* d, const ImageRef& src, float* dst, int row0, int row1,
+	hipStream_t st, const GPOut* out, const DnGamma& G )
+{
+	return( dh_run( d, src, dst, row0, row1, st, out, &G ));
 }
 
 } // namespace avirhip

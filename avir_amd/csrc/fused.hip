@@ -1179,4 +1179,41 @@ int fused_run_dn16( avirhip_plan* p, const ImageRef& src, float* dst, int row0,
 		( iout != nullptr ? &O : nullptr )));
 }
 
+// Mode 2 of a plan with sRGB gamma and 8-bit pixels on a side (k_dnfh's DH_S8
+// kinds, dnf.hip): a uint8 RGBA source read and linearised where it lies, a
+// uint8 result de-linearised and stored by the kernel (`iout`), or linear float
+// RGBA rows to `dst`. The stages' constants are launch_pack_gamma's and
+// launch_epilogue's for uint8. 1: the call takes fused_run's road.
+int fused_run_dnsrgb( avirhip_plan* p, const ImageRef& src, float* dst,
+	int row0, int row1, hipStream_t st, void* iout )
+{
+	const FusedData* F = (const FusedData*) p -> fused;
+
+	if( !fused_dn16( p ) || !p -> gamma )
+	{
+		return( 1 );
+	}
+
+	GPOut O;
+
+	if( iout != nullptr )
+	{
+		gp_make_out( p, iout, O );
+	}
+
+	DnGamma G;
+	G.tbl = p -> d_srgb_tbl;
+	G.thr = p -> d_gthr;
+	G.alpha_index = p -> alpha_index;
+	G.use_tr = ( p -> tr_mul != 1.0 );
+	G.gm = (float) ( 1.0 / 255.0 );
+	G.ogm = 255.0f;
+	G.tr_mul = (float) p -> tr_mul;
+	G.tr_muli = (float) ( 1.0 / p -> tr_mul );
+	G.pk_out = (float) p -> pk_out;
+
+	return( dn_run_hv8( F -> dn, src, dst, row0, row1, st,
+		( iout != nullptr ? &O : nullptr ), G ));
+}
+
 } // namespace avirhip

@@ -468,6 +468,27 @@ int dn_run_hv16( void* d, const ImageRef& src, float* dst, int row0, int row1,
 bool fused_dn16( const avirhip_plan* p );
 int fused_run_dn16( avirhip_plan* p, const ImageRef& src, float* dst, int row0,
 	int row1, hipStream_t st, void* iout );
+// ... with sRGB gamma and 8-bit pixels on a side (k_dnfh's DH_S8 kinds): what
+// the loader and the store need of the plan beside DnFParams -- the
+// linearising table of 256 floats, the 2 x 256 thresholds of the
+// de-linearising stage, and the parameters of that stage's direct branch
+// (launch_pack_gamma's gm, launch_epilogue's ogm and truncation)
+struct DnGamma
+{
+	const float* tbl; const float* thr;
+	int alpha_index, use_tr;
+	float gm, ogm, tr_mul, tr_muli, pk_out;
+};
+// dnf.hip: a uint8 RGBA source read where it lies (`src.type` AVIRHIP_U8; base
+// and pitch multiples of 4 bytes) or float RGBA rows; a uint8 result of 1-4
+// channels stored bytewise through `out`, or float RGBA rows to `dst`. 1: the
+// call is not its own (no 8-bit side, such an image, rows beyond a 32-bit
+// byte offset)
+int dn_run_hv8( void* d, const ImageRef& src, float* dst, int row0, int row1,
+	hipStream_t st, const GPOut* out, const DnGamma& G );
+// fused.hip: the call of a gamma plan whose mode 2 is the one-launch kernel
+int fused_run_dnsrgb( avirhip_plan* p, const ImageRef& src, float* dst,
+	int row0, int row1, hipStream_t st, void* iout );
 
 // gpass.hip: general-ratio pass kernels (path 5), AVIR and LANCIR RGBA float
 int gpass_prepare( avirhip_plan* p );

@@ -85,7 +85,18 @@ typedef enum avirhip_dtype {
  * the pack pass / the output stage with the same bits. Everywhere else -- the
  * tiles, gamma, CLancIR's exact-2x calls with 1-3 channels or an integer
  * result behind a half source, its generic kernels -- the pack pass widens
- * and the output stage narrows.) */
+ * and the output stage narrows.)
+ * (8-bit images with UseSRGBGamma: whole-ratio (2x, 3x) downsizing on both
+ * axes runs in one launch of k_dnfh as well, with the reference's bits. It
+ * linearises a uint8 RGBA source where it lies -- a base and a row pitch that
+ * are multiples of 4 bytes -- and de-linearises and stores a uint8 result of
+ * 1-4 channels itself, at any address (the default ditherer). The sides are
+ * independent: any other source (RGB, uint16, float, an image that misses the
+ * modulus) goes through the pack pass first -- and keeps the kernel's store
+ * for frames of up to 1,000,000 source pixels, the output stage beyond -- any
+ * other result through float rows and the output stage;
+ * AVIRHIP_VARIANT_DN_UNFUSED_IO keeps both stages.
+ * Every other gamma call takes the pack pass and the output stage.) */
 	AVIRHIP_F16 = 5,
 	/* bfloat16 elements: 16 bits holding the upper half of an IEEE binary32.
 	 * A call with bfloat16 elements is DEFINED by the same call with float

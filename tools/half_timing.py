@@ -60,8 +60,16 @@ one (k_sacc2< 4 / 5 > first), the branch-free launches alone and the pack road
 (AVIRHIP_SA16_AUTO_MINPIX). With PARENT.so also README's uint8 and float32
 accumulation rows on both builds, alternating.
 
-usage: python tools/half_timing.py [--bf16 | --lancir | --dnf | --gpass |
-       --lancgp | --sacc] [PARENT.so] [REPS=5] [ONLY]
+--dnsrgb measures whole-ratio downsizing of 8-bit images with sRGB gamma
+(CImageResizer(8), UseSRGBGamma, AlphaIndex 3) on path 2 by the same method --
+3840x2160 -> 1920x1080 and -> 1280x720 -- each call as it runs (k_dnfh's DH_S8
+kinds) and under AVIRHIP_VARIANT_DN_UNFUSED_IO (pack pass, k_dnf, output
+stage: the road before, the yardstick), alternating: RGBA uint8 -> uint8, RGBA
+uint8 -> float32, RGB uint8 -> uint8 (the store side only), and the RGBA uint8
+call without gamma for scale.
+
+usage: python tools/half_timing.py [--bf16 | --lancir | --dnf | --dnsrgb |
+       --gpass | --lancgp | --sacc] [PARENT.so] [REPS=5] [ONLY]
 (ONLY, with --gpass, --lancgp and --sacc: the shapes whose names hold one of
 these comma-separated words, e.g. "u8")"""
 import ctypes as C
@@ -271,6 +279,151 @@ def dnf_main(argv):
         print("  (b) and (c) bit-identical: %s" % same[0], flush=True)
         print("  (d) and (e) bit-identical: %s" % same[1], flush=True)
         del keep, run, first
+        torch.cuda.empty_cache()
+
+
+def dnsrgb_main(argv):
+    """--dnsrgb: the rows of the module docstring, CImageResizer(8) plans with
+    UseSRGBGamma on path 2. The unfused rows (AVIRHIP_VARIANT_DN_UNFUSED_IO)
+    are the road before k_dnfh's DH_S8 kinds and the yardstick of each pair."""
+    import numpy as np
+    import torch
+    import avir_amd
+    from avir_amd import abi, synth
+    reps = int(argv[2]) if len(argv) > 2 else 5
+    lib = abi.load()
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    header(lib, None)
+    TD = {abi.F32: torch.float32, abi.U8: torch.uint8}
+    ES = {abi.F32: 4, abi.U8: 1}
+    U = abi.VARIANT_DN_UNFUSED_IO
+    sw, sh = 3840, 2160
+    gv = avir_amd.CImageResizerVars()
+    gv.UseSRGBGamma, gv.AlphaIndex = 1, 3
+    for name, (nw, nh) in (("1080p", (1920, 1080)), ("720p", (1280, 720))):
+        rows = [("a  RGBA u8->u8 gamma fused", 4, abi.U8, abi.U8, 0, gv),
+                ("b  RGBA u8->u8 gamma pack + k_dnf + output stage", 4,
+                 abi.U8, abi.U8, U, gv),
+                ("c  RGBA u8->f32 gamma fused", 4, abi.U8, abi.F32, 0, gv),
+                ("d  RGBA u8->f32 gamma pack + k_dnf", 4, abi.U8, abi.F32, U,
+                 gv),
+                ("e  RGB u8->u8 gamma pack + fused store", 3, abi.U8, abi.U8,
+                 0, gv),
+                ("f  RGB u8->u8 gamma pack + k_dnf + output stage", 3, abi.U8,
+                 abi.U8, U, gv),
+                ("g  RGBA u8->u8 no gamma", 4, abi.U8, abi.U8, 0, None)]
+        pairs = [(rows[0][0], rows[1][0]), (rows[2][0], rows[3][0]),
+                 (rows[4][0], rows[5][0])]
+        run, keep, first = {}, [], {}
+        for tag, ch, ti, to, variant, vars_ in rows:
+            base = synth.lcg_u8((sh, sw, ch))
+            pair = sw * sh * ch * ES[ti] + nw * nh * ch * ES[to]
+            n = max(2, -(-(512 << 20) // pair))
+            ring = []
+            for i in range(n):
+                s = torch.from_numpy(np.roll(base, i, axis=0)).to(dev)
+                d = torch.empty((nh, nw, ch), dtype=TD[to], device=dev)
+                ring.append((s, d))
+            r = avir_amd.CImageResizer(8)
+            p = r.plan(sw, sh, nw, nh, ch, 0.0, vars_, ti, to)
+            abi.check(lib.avirhip_plan_set_path(p, 2), "path 2")
+            if variant:
+                abi.check(lib.avirhip_plan_set_variant(p, variant), "variant")
+            keep.append((r, ring))
+
+            def once(p=p, ring=ring):
+                t = 0.0
+                ms = C.c_double()
+                for s, d in ring:
+                    abi.check(lib.avirhip_time_resize(
+                        p, s.data_ptr(), d.data_ptr(), 1, st, C.byref(ms)),
+                        "time_resize")
+                    t += ms.value
+                return t / len(ring)
+            run[tag] = (once, pair, n, p)
+            first[tag] = ring[0][1]
+        # (row e: the store side alone, forced at this size)
+        with _env({"AVIRHIP_DNSRGB_STORE_MAXPIX": str(1 << 40)}):
+            for tag in run:  # warm-up, clocks
+                for _ in range(20):
+                    run[tag][0]()
+            torch.cuda.synchronize()
+            same = [torch.equal(first[x].view(torch.uint8),
+                                first[y].view(torch.uint8)) for x, y in pairs]
+            res = {tag: [] for tag in run}
+            loops = 20
+            for _ in range(reps):
+                for tag in run:
+                    res[tag].append(
+                        sum(run[tag][0]() for _ in range(loops)) / loops)
+        print("%s (%dx%d -> %dx%d, ResBitDepth 8, path 2), %d reps x %d ring "
+              "passes:" % (name, sw, sh, nw, nh, reps, loops))
+        for tag in run:
+            v = sorted(res[tag])
+            med = v[len(v) // 2]
+            print("  %-50s %.4f ms  (min %.4f max %.4f)  %6.1f MB/call  "
+                  "%.2f TB/s  ring %d  plan holds %.1f MB" % (
+                      tag, med, v[0], v[-1], run[tag][1] / 1e6,
+                      run[tag][1] / med / 1e9, run[tag][2],
+                      lib.avirhip_plan_device_bytes(run[tag][3]) / 1e6),
+                  flush=True)
+        for (x, y), ok in zip(pairs, same):
+            print("  (%s) and (%s) bit-identical: %s" % (x[0], y[0], ok),
+                  flush=True)
+        del keep, run, first
+        torch.cuda.empty_cache()
+    # the store side alone (RGB uint8 -> uint8: pack pass + k_dnfh< F32, S8 >
+    # against pack pass + k_dnf + output stage) by frame size: where
+    # dnsrgb_store_maxpix (api.cpp) belongs. AVIRHIP_DNSRGB_STORE_MAXPIX is
+    # read per call; every shape is a two-step plan at ResBitDepth 8.
+    gv3 = avir_amd.CImageResizerVars()
+    gv3.UseSRGBGamma = 1
+    print("store side alone, RGB u8->u8 gamma, fused store / output stage:")
+    for sw, sh, nw, nh in ((3840, 2160, 1920, 1080), (2560, 1440, 1280, 720),
+                           (1920, 1080, 960, 540), (1920, 1080, 640, 360),
+                           (1200, 800, 600, 400), (1200, 801, 400, 267),
+                           (600, 400, 300, 200), (600, 402, 200, 134)):
+        base = synth.lcg_u8((sh, sw, 3))
+        pair = sw * sh * 3 + nw * nh * 3
+        n = max(2, -(-(512 << 20) // pair))
+        ring = [(torch.from_numpy(np.roll(base, i, axis=0)).to(dev),
+                 torch.empty((nh, nw, 3), dtype=torch.uint8, device=dev))
+                for i in range(min(n, 64))]
+        keep, run = [], {}
+        for tag, variant in (("fused", 0), ("unfused", U)):
+            r = avir_amd.CImageResizer(8)
+            p = r.plan(sw, sh, nw, nh, 3, 0.0, gv3, abi.U8, abi.U8)
+            abi.check(lib.avirhip_plan_set_path(p, 2), "path 2")
+            abi.check(lib.avirhip_plan_set_variant(p, variant), "variant")
+            keep.append(r)
+
+            def once(p=p):
+                t = 0.0
+                ms = C.c_double()
+                for s, d in ring:
+                    abi.check(lib.avirhip_time_resize(
+                        p, s.data_ptr(), d.data_ptr(), 1, st, C.byref(ms)),
+                        "time_resize")
+                    t += ms.value
+                return t / len(ring)
+            run[tag] = once
+        res = {tag: [] for tag in run}
+        with _env({"AVIRHIP_DNSRGB_STORE_MAXPIX": str(1 << 40)}):
+            for tag in run:
+                for _ in range(5):
+                    run[tag]()
+            for _ in range(reps):
+                for tag in run:
+                    res[tag].append(sum(run[tag]() for _ in range(10)) / 10)
+        out = []
+        for tag in run:
+            v = sorted(res[tag])
+            out.append("%s %.4f ms (min %.4f max %.4f)" % (
+                tag, v[len(v) // 2], v[0], v[-1]))
+        print("  %dx%d -> %dx%d (%d source pixels): %s" % (
+            sw, sh, nw, nh, sw * sh, ", ".join(out)), flush=True)
+        del keep, run, ring
         torch.cuda.empty_cache()
 
 
@@ -712,6 +865,8 @@ def main():
         return lancir_main([a for a in sys.argv if a != "--lancir"])
     if "--dnf" in sys.argv:
         return dnf_main([a for a in sys.argv if a != "--dnf"])
+    if "--dnsrgb" in sys.argv:
+        return dnsrgb_main([a for a in sys.argv if a != "--dnsrgb"])
     import numpy as np
     import torch
     import avir_amd
