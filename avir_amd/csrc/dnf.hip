@@ -43,6 +43,12 @@
 //
 // Arithmetic contract: -ffp-contract=off, mul then add in the reference's tap
 // order => bit-identical to the two-pass kernels and to the reference.
+//
+// The march is written once, df_march, over the KIND of the pixels on each side
+// (how a row wave gets a source pixel into its row buffer, how a column wave's
+// lane stores its value: "source and store kinds" below). Two kernels call it:
+// k_dnf, float RGBA rows on both sides, with the timing ablations and in-kernel
+// clocks of AVIRHIP_DNF_DBG; k_dnfh, every other pair of kinds, without them.
 
 #include "gpass_dev.h"
 #include "dn_dev.h"
@@ -70,7 +76,7 @@ namespace avirhip {
 struct DnFParams
 {
 	DnAxisP H, V;
-	const float* src; long src_ss;  // floats per source row
+	const float* src; long src_ss;  // elements per source row
 	float* dst; long dst_ss;        // float RGBA rows, row dst_row0 at dst
 	int dst_row0;
 	int row_lo, row_hi;             // output rows to store
@@ -269,601 +275,29 @@ __device__ __forceinline__ void df_feed_batch( f2 ( &acc )[ 3 ],
 	} );
 }
 
-// (instrumented barrier / wait: the clocks only tick when dbg & 16)
-#define DF_TIMED( acc, stmt ) do { if( P.dbg & 16 ) { \
-	const unsigned long long t0_ = __builtin_readcyclecounter(); stmt; \
-	acc += __builtin_readcyclecounter() - t0_; } else { stmt; } } while( 0 )
-
-template< int KH, int NTH, int KV, int NTV, int DF_NHW >
-__global__ void __launch_bounds__( DF_NTHR ) k_dnf( const DnFParams P )
-{
-	unsigned long long tk_total = ( P.dbg & 16 ? __builtin_readcyclecounter() :
-		0 ), tk_dma = 0, tk_bar = 0;
-	constexpr int DF_NVW = 12 - DF_NHW;         // column waves
-	constexpr int DF_RS = 2 * DF_NHW;           // source rows per step
-	constexpr int DF_LPV = DF_W * 4 / DF_NVW;   // elements per column wave
-	// phases of the column waves' unroll: steps per whole number of periods
-	constexpr int DF_NPH = ( DF_RS == 16 ? KV : ( KV == 3 ? 8 : 16 ));
-	static_assert( DF_NVW * DF_LPV == DF_W * 4 && ( DF_NPH * DF_RS ) %
-		( 16 * KV ) == 0, "column wave geometry" );
-	constexpr int NPH = ( KH * ( DF_NT1 - 1 ) + NTH + 63 ) / 64; // DMA pieces
-	constexpr int ROWPX = NPH * 64;
-	constexpr int NIN = NTH + 2 * KH; // inputs of a lane's three outputs
-	constexpr int BI = NIN / 4;       // ... in four batches
-	static_assert( KH != 2 || NPH == 2, "plane layout assumes two pieces" );
-	static_assert(( NTH & 1 ) == 0 && BI * 4 == NIN, "tap pairs, batches" );
-
-	__shared__ __attribute__(( aligned( 16 ))) f4
-		sS[ DF_NHW ][ 2 ][ 2 ][ ROWPX ];
-	__shared__ __attribute__(( aligned( 16 ))) f4 sT[ DF_NHW ][ 2 ][ DF_NT1 ];
-	__shared__ __attribute__(( aligned( 16 ))) float
-		sF[ 2 ][ DF_RS ][ DF_W * 4 ];
-
-	const int tid = threadIdx.x;
-	const int lane = tid & 63;
-	const int wave = __builtin_amdgcn_readfirstlane( tid >> 6 );
-
-	// XCD-aware dealing (workgroup b runs on XCD b % 8): an XCD's contiguous
-	// item range holds whole chunk-rows of strips, so x-neighbours, which
-	// share 53 of their source columns, share an L2
-	const int nwg = gridDim.x;
-	const int b = blockIdx.x;
-	const int xcd = b & 7;
-	const int qd = nwg >> 3;
-	const int rm = nwg & 7;
-	const int item = ( xcd < rm ? xcd * ( qd + 1 ) :
-		rm * ( qd + 1 ) + ( xcd - rm ) * qd ) + ( b >> 3 );
-
-	const int chunk = item / P.nstrips;
-	const int strip = item - chunk * P.nstrips;
-
-	// output rows of this chunk, the T rows (j) they need, the source rows
-	const int oy0 = P.row_lo + chunk * P.crows;
-	const int oy1 = min( oy0 + P.crows, P.row_hi );
-	const int vlast = P.V.out_len - 1;
-	const bool top = ( oy0 - 3 < 0 );
-	const int jstart = max( oy0 - 3, 0 );
-	const int n_u = oy1 + 3 - jstart;
-	const int n_rows = KV * ( n_u - 1 ) + NTV;
-	const int S = ( n_rows + DF_RS - 1 ) / DF_RS;
-	const int r_first = KV * jstart + P.V.c0;
-
-	if( wave < DF_NHW )
-	{
-		// ------------------------------------------------------------
-		// row waves
-		// ------------------------------------------------------------
-		const int h = wave;
-		// (constant address space: scalar loads, the taps are SGPR operands)
-		gp_cfloat* const hc = (gp_cfloat*) P.H.coef;
-		f2 cp[ NTH / 2 ];
-#pragma unroll
-		for( int m = 0; m < NTH / 2; m++ )
-		{
-			cp[ m ].x = hc[ 2 * m ];
-			cp[ m ].y = hc[ 2 * m + 1 ];
-		}
-
-		const float f0 = hc[ NTH ], f1 = hc[ NTH + 1 ], f2_ = hc[ NTH + 2 ],
-			f3 = hc[ NTH + 3 ];
-
-		const int rho = lane >> 5;        // which of the wave's two rows
-		const int tri = ( lane & 31 ) >> 1;
-		const int hf = lane & 1;
-		const int X0 = strip * DF_W - 3;  // first T output of the strip
-		const int in0 = KH * X0 + P.H.c0; // its first input pixel
-		const int olast = P.H.out_len - 1;
-		const bool edge = ( X0 < 0 || X0 + DF_NT1 - 1 > olast );
-
-		// per-lane source columns of the DMA pieces (clamped: the extended
-		// view), the same for every row
-		int voff[ NPH ];
-#pragma unroll
-		for( int q = 0; q < NPH; q++ )
-		{
-			const int px = ( KH == 2 ? lane * 2 + q : q * 64 + lane );
-			voff[ q ] = dn_clampi( in0 + px, P.H.in_len - 1 ) * 16;
-		}
-
-		const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-			(void*) P.src, 0, 0x7fffffff, 0x00020000 );
-
-		const unsigned row_b = (unsigned) P.src_ss * 4u;
-		const unsigned lds_s = (unsigned) (unsigned long) (lds_char*)
-			&sS[ h ][ 0 ][ 0 ][ 0 ];
-
-		// LDS byte address of this lane's first input in buffer 0
-		const unsigned lds_in = lds_s + ( rho * ROWPX +
-			( KH == 2 ? 3 : 9 ) * tri ) * 16 + hf * 8;
-
-		const int vin_last = P.V.in_len - 1;
-
-		auto issue = [&]( const int s )
-		{
-			const int bf = s & 1;
-#pragma unroll
-			for( int rr = 0; rr < 2; rr++ )
-			{
-				const int row = dn_clampi( r_first + s * DF_RS + 2 * h + rr,
-					vin_last );
-				const unsigned soff = (unsigned) row * row_b;
-#pragma unroll
-				for( int q = 0; q < NPH; q++ )
-				{
-					df_dma( rsrc, lds_s + (( bf * 2 + rr ) * ROWPX + q * 64 ) *
-						16, voff[ q ], soff );
-				}
-			}
-		};
-
-		issue( 0 );
-
-		for( int s = 0; s < S; s++ )
-		{
-			if( s + 1 < S )
-			{
-				if( !( P.dbg & 4 ))
-				issue( s + 1 );
-
-				if( NPH == 3 )
-				{
-					DF_TIMED( tk_dma, GP_WAIT_VM( 6 ));
-				}
-				else
-				{
-					DF_TIMED( tk_dma, GP_WAIT_VM( 4 ));
-				}
-			}
-			else
-			{
-				DF_TIMED( tk_dma, GP_WAIT_VM( 0 ));
-			}
-
-			const int bf = s & 1;
-
-			// ---- resize: 3 consecutive outputs per lane
-			if( !( P.dbg & 2 ))
-			{
-				const unsigned ad = lds_in + bf * ( 2 * ROWPX * 16 );
-				DfBatch< BI > d0, d1, d2, d3;
-				f2 acc[ 3 ];
-				acc[ 0 ] = (f2) 0.0f; acc[ 1 ] = (f2) 0.0f; acc[ 2 ] = (f2) 0.0f;
-
-				df_load_at< KH, NPH, BI, 0 >( d0, ad );
-				df_load_at< KH, NPH, BI, BI >( d1, ad );
-				df_wait< BI, BI >( d0 );
-				df_feed_batch< KH, NTH, BI, 0 >( acc, d0, cp );
-				df_load_at< KH, NPH, BI, 2 * BI >( d2, ad );
-				df_wait< BI, BI >( d1 );
-				df_feed_batch< KH, NTH, BI, BI >( acc, d1, cp );
-				df_load_at< KH, NPH, BI, 3 * BI >( d3, ad );
-				df_wait< BI, BI >( d2 );
-				df_feed_batch< KH, NTH, BI, 2 * BI >( acc, d2, cp );
-				df_wait< BI, 0 >( d3 );
-				df_feed_batch< KH, NTH, BI, 3 * BI >( acc, d3, cp );
-
-				f2* tp = (f2*) &sT[ h ][ rho ][ 3 * tri ] + hf;
-				tp[ 0 ] = acc[ 0 ];
-				tp[ 2 ] = acc[ 1 ];
-				tp[ 4 ] = acc[ 2 ];
-			}
-
-			// ---- T values outside the array are copies of the edge values
-			// (the reference replicates the resize OUTPUT, avir.h:3227-3239)
-			if( edge )
-			{
-				if( lane < DF_NT1 )
-				{
-					const int x = X0 + lane;
-
-					if( x < 0 || x > olast )
-					{
-						const int xs = dn_clampi( x, olast ) - X0;
-						const f4 v0 = sT[ h ][ 0 ][ xs ];
-						const f4 v1 = sT[ h ][ 1 ][ xs ];
-						sT[ h ][ 0 ][ lane ] = v0;
-						sT[ h ][ 1 ][ lane ] = v1;
-					}
-				}
-			}
-
-			// ---- correction FIR along x: 2 rows x 42 pixels x 2 halves
-			if( !( P.dbg & 8 ))
-#pragma unroll
-			for( int q = 0; q < 3; q++ )
-			{
-				const int task = q * 64 + lane;
-
-				if( task < 2 * DF_W * 2 )
-				{
-					const int r2 = ( task >= DF_W * 2 ? 1 : 0 );
-					const int pp = task - r2 * DF_W * 2;
-					const f2* t = (const f2*) &sT[ h ][ r2 ][ 0 ] + pp;
-					f2 a = f0 * t[ 6 ];
-					a = a + f1 * ( t[ 8 ] + t[ 4 ]);
-					a = a + f2_ * ( t[ 10 ] + t[ 2 ]);
-					a = a + f3 * ( t[ 12 ] + t[ 0 ]);
-					*( (f2*) &sF[ bf ][ 2 * h + r2 ][ 0 ] + pp ) = a;
-				}
-			}
-
-			DF_TIMED( tk_bar, __syncthreads());
-		}
-	}
-	else
-	{
-		// ------------------------------------------------------------
-		// column waves
-		// ------------------------------------------------------------
-		// (Raising the column waves' priority, s_setprio 3, moves the barrier
-		// wait from the row waves -- 28 % of their time at equal priority,
-		// in-kernel clocks of AVIRHIP_DNF_DBG=16 -- to the column waves, 47 %,
-		// and the launch takes as long: the step is bound by the SIMDs' total
-		// issue, not by one role. Skewing the row waves of a SIMD against each
-		// other with s_sleep costs 3-5 %.)
-		// K = 2 along y: the column waves are the step's longest instruction
-		// streams (12 taps and a correction-filter row every second source
-		// row) and the row waves spend 40 % of their time in the barrier;
-		// raised, a column wave issues whenever it can (3840x2160 ->
-		// 1920x1080: 0.0636 -> 0.0615 ms)
-		if( KV == 2 )
-		{
-			__builtin_amdgcn_s_setprio( 3 );
-		}
-
-		const int vi = wave - DF_NHW;
-		const bool lane_ok = ( lane < DF_LPV );
-		const int e = DF_LPV * vi + ( lane_ok ? lane : DF_LPV - 1 );
-		const int x = strip * DF_W + ( e >> 2 );
-		const int ch = e & 3;
-		const bool st_ok = ( lane_ok && x < P.H.out_len );
-
-		// the tap pairs (see DF_VSTMT): one copy per lane, in registers
-		f2 k2[ NTV + 2 * KV ];
-		{
-			const f2* const v2 = (const f2*) ( P.V.coef + NTV + 4 );
-#pragma unroll
-			for( int i = 0; i < NTV + 2 * KV; i++ )
-			{
-				k2[ i ] = v2[ i ];
-			}
-#pragma unroll
-			for( int i = 0; i < NTV + 2 * KV; i++ )
-			{
-				asm volatile( "" : "+v"( k2[ i ])); // (no re-loading later)
-			}
-		}
-
-		gp_cfloat* const vc = (gp_cfloat*) P.V.coef;
-		const float f0 = vc[ NTV ], f1 = vc[ NTV + 1 ], f2_ = vc[ NTV + 2 ],
-			f3 = vc[ NTV + 3 ];
-
-		// destination: lane offset fixed, row offset scalar; lanes that must
-		// not store get an offset the buffer range check drops
-		int st_voff;
-		__amdgpu_buffer_rsrc_t drs;
-
-		if( P.out.on != 0 )
-		{
-			const int es = ( P.out.type == AVIRHIP_U8 ? 1 :
-				( P.out.type == AVIRHIP_U16 ? 2 : 4 ));
-
-			drs = __builtin_amdgcn_make_buffer_rsrc( P.out.base, 0,
-				0x7fffffff, 0x00020000 );
-			st_voff = ( st_ok && ch < P.out.ch ?
-				( x * P.out.ch + ch ) * es : (int) 0x80000000 );
-		}
-		else
-		{
-			drs = __builtin_amdgcn_make_buffer_rsrc( (void*) P.dst, 0,
-				0x7fffffff, 0x00020000 );
-			st_voff = ( st_ok ? ( x * 4 + ch ) * 4 : (int) 0x80000000 );
-		}
-
-		f2 accp[ 8 ];
-		float wr[ 8 ];
-#pragma unroll
-		for( int i = 0; i < 8; i++ )
-		{
-			accp[ i ] = (f2) 0.0f;
-			wr[ i ] = 0.0f;
-		}
-
-		int s = 0;
-		int jl_base = 0; // local index of the output in slot 0 of this period
-
-		while( s < S )
-		{
-			dn_static_for< DF_NPH >( [&]( auto phc )
-			{
-				constexpr int ph = decltype( phc )::value;
-
-				if( s < S )
-				{
-					DF_TIMED( tk_bar, __syncthreads());
-					f2 vp[ DF_RS / 2 ];
-#pragma unroll
-					for( int m = 0; m < DF_RS / 2; m++ )
-					{
-						vp[ m ].x = sF[ s & 1 ][ 2 * m ][ e ];
-						vp[ m ].y = sF[ s & 1 ][ 2 * m + 1 ][ e ];
-					}
-
-					if( !( P.dbg & 1 ))
-					dn_static_for< DF_RS >( [&]( auto ic )
-					{
-						constexpr int i = decltype( ic )::value;
-						constexpr int u = ph * DF_RS + i; // row of the period
-						constexpr DfRow< KV, NTV, u > R;
-
-						// the sum of an output starts from +0.0f
-						if constexpr( R.zslot >= 0 )
-						{
-							constexpr int zp = ( R.zslot >> 2 ) * 2 +
-								( R.zslot & 1 );
-
-							if constexpr((( R.zslot >> 1 ) & 1 ) == 0 )
-							{
-								accp[ zp ].x = 0.0f;
-							}
-							else
-							{
-								accp[ zp ].y = 0.0f;
-							}
-						}
-
-#define DF_PI( k ) accp[ R.pi[ ( k ) < R.n ? ( k ) : 0 ]]
-#define DF_KI( k ) k2[ R.vi[ ( k ) < R.n ? ( k ) : 0 ]]
-						df_vstmt< R.n, ( i & 1 ) >( DF_PI( 0 ), DF_PI( 1 ),
-							DF_PI( 2 ), DF_PI( 3 ), DF_PI( 4 ), DF_PI( 5 ),
-							DF_PI( 6 ), DF_PI( 7 ), vp[ i >> 1 ], DF_KI( 0 ),
-							DF_KI( 1 ), DF_KI( 2 ), DF_KI( 3 ), DF_KI( 4 ),
-							DF_KI( 5 ), DF_KI( 6 ), DF_KI( 7 ));
-#undef DF_PI
-#undef DF_KI
-
-						// a T row completes with its last tap
-						if constexpr(( u - ( NTV - 1 )) % KV == 0 )
-						{
-							constexpr int jp = ( u - ( NTV - 1 )) / KV;
-							constexpr int slot = (( jp % 16 ) + 16 ) % 16;
-							constexpr int sp = ( slot >> 2 ) * 2 + ( slot & 1 );
-							constexpr int ws = (( jp % 8 ) + 8 ) % 8;
-							const int jl = jl_base + jp;
-
-							if( jl >= 0 )
-							{
-								const int j = jstart + jl;
-								float U = ((( slot >> 1 ) & 1 ) == 0 ?
-									accp[ sp ].x : accp[ sp ].y );
-
-								if( j > vlast )
-								{
-									U = wr[ ( ws + 7 ) & 7 ];
-								}
-
-								if( jl == 0 && top )
-								{
-#pragma unroll
-									for( int k = 0; k < 8; k++ )
-									{
-										wr[ k ] = U;
-									}
-								}
-
-								wr[ ws ] = U;
-								const int y = j - 3;
-
-								if( y >= oy0 && y < oy1 )
-								{
-									float a = f0 * wr[ ( ws + 5 ) & 7 ];
-									a = a + f1 * ( wr[ ( ws + 6 ) & 7 ] +
-										wr[ ( ws + 4 ) & 7 ]);
-									a = a + f2_ * ( wr[ ( ws + 7 ) & 7 ] +
-										wr[ ( ws + 3 ) & 7 ]);
-									a = a + f3 * ( wr[ ws ] +
-										wr[ ( ws + 2 ) & 7 ]);
-
-									const int yr = y - P.dst_row0;
-
-									if( P.out.on == 0 )
-									{
-										__builtin_amdgcn_raw_buffer_store_b32(
-											__builtin_bit_cast( unsigned, a ),
-											drs, st_voff,
-											yr * (int) P.dst_ss * 4, 0 );
-									}
-									else
-									{
-										df_store_elem( P.out, drs, st_voff, yr,
-											a );
-									}
-								}
-							}
-						}
-					} );
-
-					s++;
-				}
-			} );
-
-			jl_base += DF_NPH * DF_RS / KV;
-		}
-	}
-
-	if(( P.dbg & 16 ) && lane == 0 && P.clk != nullptr )
-	{
-		unsigned long long* const q = P.clk + ( (size_t) item * 12 + wave ) * 4;
-		q[ 0 ] = __builtin_readcyclecounter() - tk_total;
-		q[ 1 ] = tk_dma; q[ 2 ] = tk_bar; q[ 3 ] = (unsigned long long) S;
-	}
-}
-
 // ---------------------------------------------------------------------
-// host side
-// ---------------------------------------------------------------------
-
-static DnAxisP dnf_axis( const DnAxis& A )
-{
-	DnAxisP P;
-	P.K = A.K; P.NT = A.NT; P.c0 = A.c0;
-	P.in_len = A.in_len; P.out_len = A.out_len; P.coef = A.d_coef;
-	return( P );
-}
-
-// Both axes in one launch: float RGBA source rows -> destination rows
-// [row0, row1) (row row0 at `dst`, or through the integer output stage `out`).
-// Returns 1 when this call cannot take the fused kernel.
-int dn_run_hv( void* d, const float* src, long src_ss, float* dst, int row0,
-	int row1, hipStream_t st, const GPOut* out )
-{
-	const DnData* D = (const DnData*) d;
-
-	if( D == nullptr || !D -> hok || !D -> vok )
-	{
-		return( 1 );
-	}
-
-	if( row1 <= row0 )
-	{
-		return( AVIRHIP_OK );
-	}
-
-	// (row offsets of the DMA are 32-bit)
-	if( (long) D -> v.in_len * src_ss * 4 >= 0x7fffffffL )
-	{
-		return( 1 );
-	}
-
-	DnFParams P;
-	P.H = dnf_axis( D -> h );
-	P.V = dnf_axis( D -> v );
-	P.src = src; P.src_ss = src_ss;
-	P.dst = dst; P.dst_ss = (long) D -> h.out_len * 4; P.dst_row0 = row0;
-	P.row_lo = row0; P.row_hi = row1;
-	memset( &P.out, 0, sizeof( P.out ));
-
-	if( out != nullptr )
-	{
-		P.out = *out;
-	}
-
-	static const int dbg = []() { const char* e = getenv( "AVIRHIP_DNF_DBG" );
-		return( e != nullptr ? atoi( e ) : 0 ); }();
-	P.dbg = dbg;
-	P.clk = nullptr;
-	static unsigned long long* dclk = nullptr;
-	static int dcalls = 0;
-
-
-	P.nstrips = ( D -> h.out_len + DF_W - 1 ) / DF_W;
-	const int rows = row1 - row0;
-	P.crows = dnf_chunk_rows( rows, D -> ncu, P.nstrips );
-	P.nchunks = ( rows + P.crows - 1 ) / P.crows;
-	const dim3 grid( P.nstrips * P.nchunks );
-
-	// (debugging aid, single-threaded use: per-wave clocks of up to 4096 work
-	// items; larger launches and a failed allocation run without them)
-	if(( dbg & 16 ) && grid.x <= 4096 )
-	{
-		if( dclk == nullptr && hipMalloc( &dclk, 4096 * 12 * 32 ) != hipSuccess )
-		{
-			(void) hipGetLastError();
-			dclk = nullptr;
-		}
-
-		P.clk = dclk;
-	}
-	const int kk = D -> h.K * 10 + D -> v.K;
-	// K = 3 along y: 9 row waves + 3 column waves (AVIRHIP_DNF_NHW=8: the 8 + 4
-	// split, for A/B timing)
-	static const int nhw3 = []() { const char* e = getenv( "AVIRHIP_DNF_NHW" );
-		return( e != nullptr && atoi( e ) == 8 ? 8 : 9 ); }();
-
-#define DF_LAUNCH( ... ) hipLaunchKernelGGL(( k_dnf< __VA_ARGS__ > ), grid, \
-	dim3( DF_NTHR ), 0, st, P )
-
-	switch( kk )
-	{
-		case 33:
-			if( nhw3 == 9 ) DF_LAUNCH( 3, 38, 3, 38, 9 );
-			else DF_LAUNCH( 3, 38, 3, 38, 8 );
-			break;
-		case 22:
-			DF_LAUNCH( 2, 24, 2, 24, 8 );
-			break;
-		case 32:
-			DF_LAUNCH( 3, 38, 2, 24, 8 );
-			break;
-		case 23:
-			if( nhw3 == 9 ) DF_LAUNCH( 2, 24, 3, 38, 9 );
-			else DF_LAUNCH( 2, 24, 3, 38, 8 );
-			break;
-		default:
-			return( 1 );
-	}
-
-#undef DF_LAUNCH
-	dnf_verbose( "k_dnf", P.nstrips, P.nchunks, P.crows );
-
-	if(( dbg & 16 ) && P.clk != nullptr && ++dcalls == 100 )
-	{
-		// in-kernel clocks of a launch in the middle of a timing loop
-		std::vector< unsigned long long > hc( (size_t) grid.x * 12 * 4 );
-		(void) hipStreamSynchronize( st );
-		(void) hipMemcpy( hc.data(), dclk, hc.size() * 8, hipMemcpyDeviceToHost );
-		const int nh = ( D -> v.K == 3 ? nhw3 : 8 );
-		double tot[ 2 ] = { 0, 0 }, dma[ 2 ] = { 0, 0 }, bar[ 2 ] = { 0, 0 };
-		double mx = 0.0;
-
-		for( unsigned i = 0; i < grid.x; i++ )
-		{
-			for( int wv = 0; wv < 12; wv++ )
-			{
-				const unsigned long long* q = &hc[ ( (size_t) i * 12 + wv ) * 4 ];
-				const int r = ( wv < nh ? 0 : 1 );
-				tot[ r ] += (double) q[ 0 ]; dma[ r ] += (double) q[ 1 ];
-				bar[ r ] += (double) q[ 2 ];
-				mx = std::max( mx, (double) q[ 0 ]);
-			}
-		}
-
-		const double nr = (double) grid.x * nh, nc = (double) grid.x * ( 12 - nh );
-		fprintf( stderr, "k_dnf clocks (%u items, %d row waves): row waves total "
-			"%.0f, DMA wait %.0f, barrier %.0f | column waves total %.0f, "
-			"barrier %.0f | longest wave %.0f cycles, %llu steps\n", grid.x, nh,
-			tot[ 0 ] / nr, dma[ 0 ] / nr, bar[ 0 ] / nr, tot[ 1 ] / nc,
-			bar[ 1 ] / nc, mx, hc[ 3 ]);
-	}
-	AVIRHIP_HIPCHECK( hipGetLastError() );
-	return( AVIRHIP_OK );
-}
-
-// ---------------------------------------------------------------------
-// k_dnfh: k_dnf with half / bfloat16 pixels on a side, in the same launch
+// source and store kinds
 // ---------------------------------------------------------------------
 //
-// k_dnf's march and arithmetic, statement for statement (its row and column
-// roles, strips, chunks, tap order: see the head of this file), with
-//   SRC  DH_F16 / DH_BF16: the row waves read the caller's 16-bit RGBA rows
+// The march's row and column roles, strips, chunks and tap order (the head of
+// this file) are the same for every kind; a kind decides
+//   SRC  DH_F32: float RGBA rows, by LDS-DMA one step ahead.
+//        DH_F16 / DH_BF16: the row waves read the caller's 16-bit RGBA rows
 //        where they lie. LDS-DMA has no 8-byte form, so a lane takes its pixel
 //        of each piece with ONE 8-byte buffer load into registers, issued one
-//        step ahead where k_dnf issues the DMA (2 rows x NPH pieces x 2
-//        VGPRs), and at the head of the step widens it exactly (half:
+//        step ahead where a float source issues the DMA (2 rows x NPH pieces
+//        x 2 VGPRs), and at the head of the step widens it exactly (half:
 //        v_cvt_f32_f16, denormals kept; bfloat16: bits << 16) and writes it
 //        with one ds_write_b128 into the slot of sS the DMA would have filled
 //        (lane l of piece q: slot q * 64 + l -- for K = 2 that IS df_slot's
 //        even / odd plane layout, the lane's pixel being 2 l + q). The row
 //        buffers are wave-private: an lgkmcnt wait between the writes and the
-//        window reads, no barrier. Everything behind sS is k_dnf's.
-//        DH_F32: float RGBA rows by k_dnf's LDS-DMA.
-//   OUT  DH_F16 / DH_BF16: a column wave's lane narrows its channel (half:
+//        window reads, no barrier. Everything behind sS is the same.
+//   OUT  DH_F32: float RGBA rows, or the integer output stage (df_store_elem).
+//        DH_F16 / DH_BF16: a column wave's lane narrows its channel (half:
 //        v_cvt_f16_f32, nearest even, never the pkrtz form; bfloat16:
 //        v_cvt_pk_bf16_f32, low half) and stores 2 bytes at
 //        ( x * ch + c ) * 2 of the caller's row.
-//        DH_F32: k_dnf's stores (float RGBA rows, or df_store_elem).
-// Float on both sides is k_dnf's own and is not instantiated. The timing
-// ablations of AVIRHIP_DNF_DBG are k_dnf's alone.
 //
 // With sRGB gamma (DnSParams; dnsrgb_dev.h has the stages' expressions):
 //   SRC  DH_S8: the caller's uint8 RGBA rows. ONE 4-byte buffer load per
@@ -1012,29 +446,10 @@ __device__ __forceinline__ unsigned short dh_narrow( const float v )
 	}
 }
 
-// the registers of a step's loads, once all of them have returned
-template< int NP >
-__device__ __forceinline__ void dh_wait_raw( dh_u2 ( &r )[ 2 ][ NP ])
-{
-	static_assert( NP == 2 || NP == 3, "pieces per row" );
-
-	if constexpr( NP == 3 )
-	{
-		asm volatile( AVIRHIP_WAITCNT_VM( 0 )
-			: "+v"( r[ 0 ][ 0 ]), "+v"( r[ 0 ][ 1 ]), "+v"( r[ 0 ][ 2 ]),
-			"+v"( r[ 1 ][ 0 ]), "+v"( r[ 1 ][ 1 ]), "+v"( r[ 1 ][ 2 ])
-			:: "memory" );
-	}
-	else
-	{
-		asm volatile( AVIRHIP_WAITCNT_VM( 0 )
-			: "+v"( r[ 0 ][ 0 ]), "+v"( r[ 0 ][ 1 ]), "+v"( r[ 1 ][ 0 ]),
-			"+v"( r[ 1 ][ 1 ]) :: "memory" );
-	}
-}
-
-template< int NP >
-__device__ __forceinline__ void dh_wait_raw( unsigned int ( &r )[ 2 ][ NP ])
+// the registers of a step's loads (dh_u2 or unsigned int each), once all of
+// them have returned
+template< class T, int NP >
+__device__ __forceinline__ void dh_wait_raw( T ( &r )[ 2 ][ NP ])
 {
 	static_assert( NP == 2 || NP == 3, "pieces per row" );
 
@@ -1109,15 +524,28 @@ __device__ __forceinline__ void dh_fill_tables( const DnGamma& G,
 	}
 }
 
-template< int KH, int NTH, int KV, int NTV, int DF_NHW, int SRC, int OUT >
-__global__ void __launch_bounds__( DF_NTHR ) k_dnfh(
-	const typename DhParams< SRC, OUT >::type PA )
+// ---------------------------------------------------------------------
+// the march
+// ---------------------------------------------------------------------
+
+// (instrumented barrier / wait: the clocks only tick when dbg & 16)
+#define DF_TIMED( acc, stmt ) do { if( dbg & 16 ) { \
+	const unsigned long long t0_ = __builtin_readcyclecounter(); stmt; \
+	acc += __builtin_readcyclecounter() - t0_; } else { stmt; } } while( 0 )
+
+// A workgroup's whole march, for the kernels below to call. SRC, OUT: the kinds
+// above; PT: DnFParams, or DnSParams with a DH_S8 side. DBG: the timing
+// ablations of DnFParams::dbg and the in-kernel clocks are in the code; without
+// it `dbg` is the constant 0 and none of them is.
+template< int KH, int NTH, int KV, int NTV, int DF_NHW, int SRC, int OUT,
+	bool DBG, class PT >
+__device__ __forceinline__ void df_march( const PT& PA )
 {
-	static_assert( SRC != DH_F32 || OUT != DH_F32, "float -> float is k_dnf" );
 	constexpr bool S8 = ( SRC == DH_S8 || OUT == DH_S8 );
-	static_assert( !S8 || (( SRC == DH_S8 || SRC == DH_F32 ) &&
-		( OUT == DH_S8 || OUT == DH_F32 )), "gamma: uint8 and float sides" );
 	const DnFParams& P = dh_core( PA );
+	const int dbg = ( DBG ? P.dbg : 0 );
+	unsigned long long tk_total = ( dbg & 16 ? __builtin_readcyclecounter() :
+		0 ), tk_dma = 0, tk_bar = 0;
 	constexpr int DF_NVW = 12 - DF_NHW;         // column waves
 	constexpr int DF_RS = 2 * DF_NHW;           // source rows per step
 	constexpr int DF_LPV = DF_W * 4 / DF_NVW;   // elements per column wave
@@ -1285,20 +713,21 @@ __global__ void __launch_bounds__( DF_NTHR ) k_dnfh(
 			{
 				if( s + 1 < S )
 				{
+					if( !( dbg & 4 ))
 					issue( s + 1 );
 
 					if( NPH == 3 )
 					{
-						GP_WAIT_VM( 6 );
+						DF_TIMED( tk_dma, GP_WAIT_VM( 6 ));
 					}
 					else
 					{
-						GP_WAIT_VM( 4 );
+						DF_TIMED( tk_dma, GP_WAIT_VM( 4 ));
 					}
 				}
 				else
 				{
-					GP_WAIT_VM( 0 );
+					DF_TIMED( tk_dma, GP_WAIT_VM( 0 ));
 				}
 			}
 			else
@@ -1306,7 +735,7 @@ __global__ void __launch_bounds__( DF_NTHR ) k_dnfh(
 				// this step's pixels have landed in the registers (the only
 				// vector-memory loads of a row wave in flight are theirs):
 				// widen, write the slots, send for the next step's
-				dh_wait_raw< NPH >( raw );
+				dh_wait_raw( raw );
 				const unsigned wad = lds_w + bf * ( 2 * ROWPX * 16 );
 #pragma unroll
 				for( int q = 0; q < NPH; q++ )
@@ -1338,6 +767,7 @@ __global__ void __launch_bounds__( DF_NTHR ) k_dnfh(
 			}
 
 			// ---- resize: 3 consecutive outputs per lane
+			if( !( dbg & 2 ))
 			{
 				const unsigned ad = lds_in + bf * ( 2 * ROWPX * 16 );
 				DfBatch< BI > d0, d1, d2, d3;
@@ -1383,6 +813,7 @@ __global__ void __launch_bounds__( DF_NTHR ) k_dnfh(
 			}
 
 			// ---- correction FIR along x: 2 rows x 42 pixels x 2 halves
+			if( !( dbg & 8 ))
 #pragma unroll
 			for( int q = 0; q < 3; q++ )
 			{
@@ -1401,7 +832,7 @@ __global__ void __launch_bounds__( DF_NTHR ) k_dnfh(
 				}
 			}
 
-			__syncthreads();
+			DF_TIMED( tk_bar, __syncthreads());
 		}
 	}
 	else
@@ -1516,7 +947,7 @@ __global__ void __launch_bounds__( DF_NTHR ) k_dnfh(
 
 				if( s < S )
 				{
-					__syncthreads();
+					DF_TIMED( tk_bar, __syncthreads());
 
 					if constexpr( OUT == DH_S8 )
 					{
@@ -1535,6 +966,7 @@ __global__ void __launch_bounds__( DF_NTHR ) k_dnfh(
 						vp[ m ].y = sF[ s & 1 ][ 2 * m + 1 ][ e ];
 					}
 
+					if( !( dbg & 1 ))
 					dn_static_for< DF_RS >( [&]( auto ic )
 					{
 						constexpr int i = decltype( ic )::value;
@@ -1700,6 +1132,181 @@ __global__ void __launch_bounds__( DF_NTHR ) k_dnfh(
 		}
 	}
 
+	if(( dbg & 16 ) && lane == 0 && P.clk != nullptr )
+	{
+		unsigned long long* const q = P.clk + ( (size_t) item * 12 + wave ) * 4;
+		q[ 0 ] = __builtin_readcyclecounter() - tk_total;
+		q[ 1 ] = tk_dma; q[ 2 ] = tk_bar; q[ 3 ] = (unsigned long long) S;
+	}
+}
+
+// float RGBA rows on both sides, with the ablations and the clocks
+template< int KH, int NTH, int KV, int NTV, int DF_NHW >
+__global__ void __launch_bounds__( DF_NTHR ) k_dnf( const DnFParams P )
+{
+	df_march< KH, NTH, KV, NTV, DF_NHW, DH_F32, DH_F32, true >( P );
+}
+
+// every other pair of kinds
+template< int KH, int NTH, int KV, int NTV, int DF_NHW, int SRC, int OUT >
+__global__ void __launch_bounds__( DF_NTHR ) k_dnfh(
+	const typename DhParams< SRC, OUT >::type PA )
+{
+	static_assert( SRC != DH_F32 || OUT != DH_F32, "float -> float is k_dnf" );
+	constexpr bool S8 = ( SRC == DH_S8 || OUT == DH_S8 );
+	static_assert( !S8 || (( SRC == DH_S8 || SRC == DH_F32 ) &&
+		( OUT == DH_S8 || OUT == DH_F32 )), "gamma: uint8 and float sides" );
+	df_march< KH, NTH, KV, NTV, DF_NHW, SRC, OUT, false >( PA );
+}
+
+// ---------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------
+
+static DnAxisP dnf_axis( const DnAxis& A )
+{
+	DnAxisP P;
+	P.K = A.K; P.NT = A.NT; P.c0 = A.c0;
+	P.in_len = A.in_len; P.out_len = A.out_len; P.coef = A.d_coef;
+	return( P );
+}
+
+// A launch's parameters: both axes of the plan, the source rows (`src_ss`
+// elements of their type apart), destination rows [row0, row1), the output
+// stage if there is one, and the chunk rule -- the grid is nstrips * nchunks
+// work items. No ablations, no clocks.
+static void dnf_fill( DnFParams& P, const DnData* D, const void* src,
+	long src_ss, float* dst, int row0, int row1, const GPOut* out )
+{
+	P.H = dnf_axis( D -> h );
+	P.V = dnf_axis( D -> v );
+	P.src = (const float*) src; P.src_ss = src_ss;
+	P.dst = dst; P.dst_ss = (long) D -> h.out_len * 4; P.dst_row0 = row0;
+	P.row_lo = row0; P.row_hi = row1;
+	memset( &P.out, 0, sizeof( P.out ));
+
+	if( out != nullptr )
+	{
+		P.out = *out;
+	}
+
+	P.dbg = 0;
+	P.clk = nullptr;
+	P.nstrips = ( D -> h.out_len + DF_W - 1 ) / DF_W;
+	const int rows = row1 - row0;
+	P.crows = dnf_chunk_rows( rows, D -> ncu, P.nstrips );
+	P.nchunks = ( rows + P.crows - 1 ) / P.crows;
+}
+
+// Both axes in one launch: float RGBA source rows -> destination rows
+// [row0, row1) (row row0 at `dst`, or through the integer output stage `out`).
+// Returns 1 when this call cannot take the fused kernel.
+int dn_run_hv( void* d, const float* src, long src_ss, float* dst, int row0,
+	int row1, hipStream_t st, const GPOut* out )
+{
+	const DnData* D = (const DnData*) d;
+
+	if( D == nullptr || !D -> hok || !D -> vok )
+	{
+		return( 1 );
+	}
+
+	if( row1 <= row0 )
+	{
+		return( AVIRHIP_OK );
+	}
+
+	// (row offsets of the DMA are 32-bit)
+	if( (long) D -> v.in_len * src_ss * 4 >= 0x7fffffffL )
+	{
+		return( 1 );
+	}
+
+	DnFParams P;
+	dnf_fill( P, D, src, src_ss, dst, row0, row1, out );
+	const dim3 grid( P.nstrips * P.nchunks );
+
+	static const int dbg = []() { const char* e = getenv( "AVIRHIP_DNF_DBG" );
+		return( e != nullptr ? atoi( e ) : 0 ); }();
+	P.dbg = dbg;
+	static unsigned long long* dclk = nullptr;
+	static int dcalls = 0;
+
+	// (debugging aid, single-threaded use: per-wave clocks of up to 4096 work
+	// items; larger launches and a failed allocation run without them)
+	if(( dbg & 16 ) && grid.x <= 4096 )
+	{
+		if( dclk == nullptr && hipMalloc( &dclk, 4096 * 12 * 32 ) != hipSuccess )
+		{
+			(void) hipGetLastError();
+			dclk = nullptr;
+		}
+
+		P.clk = dclk;
+	}
+	const int kk = D -> h.K * 10 + D -> v.K;
+	// K = 3 along y: 9 row waves + 3 column waves (AVIRHIP_DNF_NHW=8: the 8 + 4
+	// split, for A/B timing)
+	static const int nhw3 = []() { const char* e = getenv( "AVIRHIP_DNF_NHW" );
+		return( e != nullptr && atoi( e ) == 8 ? 8 : 9 ); }();
+
+#define DF_LAUNCH( ... ) hipLaunchKernelGGL(( k_dnf< __VA_ARGS__ > ), grid, \
+	dim3( DF_NTHR ), 0, st, P )
+
+	switch( kk )
+	{
+		case 33:
+			if( nhw3 == 9 ) DF_LAUNCH( 3, 38, 3, 38, 9 );
+			else DF_LAUNCH( 3, 38, 3, 38, 8 );
+			break;
+		case 22:
+			DF_LAUNCH( 2, 24, 2, 24, 8 );
+			break;
+		case 32:
+			DF_LAUNCH( 3, 38, 2, 24, 8 );
+			break;
+		case 23:
+			if( nhw3 == 9 ) DF_LAUNCH( 2, 24, 3, 38, 9 );
+			else DF_LAUNCH( 2, 24, 3, 38, 8 );
+			break;
+		default:
+			return( 1 );
+	}
+
+#undef DF_LAUNCH
+	dnf_verbose( "k_dnf", P.nstrips, P.nchunks, P.crows );
+
+	if(( dbg & 16 ) && P.clk != nullptr && ++dcalls == 100 )
+	{
+		// in-kernel clocks of a launch in the middle of a timing loop
+		std::vector< unsigned long long > hc( (size_t) grid.x * 12 * 4 );
+		(void) hipStreamSynchronize( st );
+		(void) hipMemcpy( hc.data(), dclk, hc.size() * 8, hipMemcpyDeviceToHost );
+		const int nh = ( D -> v.K == 3 ? nhw3 : 8 );
+		double tot[ 2 ] = { 0, 0 }, dma[ 2 ] = { 0, 0 }, bar[ 2 ] = { 0, 0 };
+		double mx = 0.0;
+
+		for( unsigned i = 0; i < grid.x; i++ )
+		{
+			for( int wv = 0; wv < 12; wv++ )
+			{
+				const unsigned long long* q = &hc[ ( (size_t) i * 12 + wv ) * 4 ];
+				const int r = ( wv < nh ? 0 : 1 );
+				tot[ r ] += (double) q[ 0 ]; dma[ r ] += (double) q[ 1 ];
+				bar[ r ] += (double) q[ 2 ];
+				mx = std::max( mx, (double) q[ 0 ]);
+			}
+		}
+
+		const double nr = (double) grid.x * nh, nc = (double) grid.x * ( 12 - nh );
+		fprintf( stderr, "k_dnf clocks (%u items, %d row waves): row waves total "
+			"%.0f, DMA wait %.0f, barrier %.0f | column waves total %.0f, "
+			"barrier %.0f | longest wave %.0f cycles, %llu steps\n", grid.x, nh,
+			tot[ 0 ] / nr, dma[ 0 ] / nr, bar[ 0 ] / nr, tot[ 1 ] / nc,
+			bar[ 1 ] / nc, mx, hc[ 3 ]);
+	}
+	AVIRHIP_HIPCHECK( hipGetLastError() );
+	return( AVIRHIP_OK );
 }
 
 static int dh_kind( const int type )
@@ -1779,33 +1386,14 @@ static int dh_run( void* d, const ImageRef& src, float* dst, int row0, int row1,
 
 	DnSParams PS;
 	DnFParams& P = PS.F;
-	P.H = dnf_axis( D -> h );
-	P.V = dnf_axis( D -> v );
-	P.src = (const float*) src.ptr; P.src_ss = src.stride; // (elements)
-	P.dst = dst; P.dst_ss = (long) D -> h.out_len * 4; P.dst_row0 = row0;
-	P.row_lo = row0; P.row_hi = row1;
-	memset( &P.out, 0, sizeof( P.out ));
+	dnf_fill( P, D, src.ptr, src.stride, dst, row0, row1, out );
+	const dim3 grid( P.nstrips * P.nchunks );
 	memset( &PS.G, 0, sizeof( PS.G ));
-
-	if( out != nullptr )
-	{
-		P.out = *out;
-	}
 
 	if( G != nullptr )
 	{
 		PS.G = *G;
 	}
-
-	P.dbg = 0;
-	P.clk = nullptr;
-
-	// (dn_run_hv's chunk rule)
-	P.nstrips = ( D -> h.out_len + DF_W - 1 ) / DF_W;
-	const int rows = row1 - row0;
-	P.crows = dnf_chunk_rows( rows, D -> ncu, P.nstrips );
-	P.nchunks = ( rows + P.crows - 1 ) / P.crows;
-	const dim3 grid( P.nstrips * P.nchunks );
 
 #define DH_LAUNCH( SK, OK ) hipLaunchKernelGGL(( k_dnfh< KH, NTH, KV, NTV, NHW, \
 	SK, OK > ), grid, dim3( DF_NTHR ), 0, st, P )

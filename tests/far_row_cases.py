@@ -89,7 +89,7 @@ L_GPASS = _lim(
     "gpass.hip:971",
     "if( (long) p -> src_h * p -> src_stride * 4 >= ( 1L << 31 ) ||")
 L_DNF = _lim(
-    "sh * pitch * 4", "<", 0x7fffffff, "bytes", "dnf.hip:733",
+    "sh * pitch * 4", "<", 0x7fffffff, "bytes", "dnf.hip:1220",
     "if( (long) D -> v.in_len * src_ss * 4 >= 0x7fffffffL )")
 L_LANC2 = _lim(
     "sh * pitch", "<", GIB2, "elements", "lanc2.hip:616",
