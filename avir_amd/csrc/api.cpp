@@ -596,9 +596,27 @@ void need_range( const LOp& op, int a, int b, int& ia, int& ib )
 	ib = std::max( 0, std::min( ib, op.in_len - 1 ));
 }
 
+// An AVIR plan's kernels read float pixels of the plan's channel count, without
+// gamma: any other source goes through the pack pass's copy (`packed`)
+static bool avir_need_pack( const avirhip_plan* p )
+{
+	return( p -> gamma || p -> in_type != AVIRHIP_F32 || p -> ch != p -> io_ch );
+}
+
+// float output is the vertical pass' in-place result (avir.h:4956-4979):
+// with gamma it stays linear, only the other output types are
+// de-linearised in the epilogue
+// (fpclass_float4 has no in-place output: its float results pass through
+// the output stage like every other type, which matters with gamma)
+static bool avir_direct( const avirhip_plan* p )
+{
+	return( p -> out_type == AVIRHIP_F32 && p -> ch == p -> io_ch &&
+		!( p -> fp4 && p -> gamma ));
+}
+
 // The float copies a call may need, allocated up front: every road but
-// k_dnfh's (avir_dn16) and the pass kernels' with half / bfloat16 pixels on a
-// side (exec_avir) calls this first. Those skip it, and avir_pack (`packed`)
+// k_dnfh's and the pass kernels' with half / bfloat16 pixels on a side
+// (avir_road: `lazy`) calls this first. Those skip it, and avir_pack (`packed`)
 // and avir_need_res (`resbuf`) allocate each when something is about to use it
 // -- the same sizes as here, so after this function they are no-ops.
 static int ensure_scratch( avirhip_plan* p )
@@ -617,12 +635,11 @@ static int ensure_scratch( avirhip_plan* p )
 		return( AVIRHIP_OK );
 	}
 
-	if(( p -> in_type != AVIRHIP_F32 || p -> gamma || p -> ch != p -> io_ch ) &&
+	if( avir_need_pack( p ) &&
 		( rc = need_floats( p, &p -> packed, (size_t) p -> src_w * p -> src_h *
 		p -> ch )) != 0 ) return( rc );
 
-	if(( p -> out_type != AVIRHIP_F32 || p -> ch != p -> io_ch ||
-		( p -> fp4 && p -> gamma )) &&
+	if( !avir_direct( p ) &&
 		( rc = need_floats( p, &p -> resbuf, (size_t) p -> new_w * p -> new_h *
 		p -> ch )) != 0 ) return( rc );
 
@@ -1107,47 +1124,326 @@ static int lancir_owner( avirhip_plan* p, const void* src, void* dst,
 
 // ---- AVIR ----
 
-// The source of one AVIR call: the caller's image, and the float image the
-// kernels read -- the caller's own (float pixels of the plan's channel count,
-// no gamma), or the plan's `packed` copy, which the pack pass fills at most
-// once per call and only when a kernel is about to read it.
-struct AvirSrc
+// What belongs to one AVIR call. Two things change while it runs, here and
+// nowhere else. The float image the kernels read: the caller's own (float
+// pixels of the plan's channel count, no gamma), or the plan's `packed` copy,
+// which the pack pass fills at most once per call and only when a kernel is
+// about to read it (avir_pack). The float result: the caller's image when
+// `direct`, else the plan's `resbuf` -- null until something asked for it.
+struct AvirCall
 {
-	const void* img;
-	const float* f;
+	avirhip_plan* p;
+	int path;
+	ImageRef img;       // the caller's source
+	void* dst;          // the caller's result
+	int row0, row1;
+	hipStream_t st;
+	SrcWindow win;
+	bool need_pack;     // avir_need_pack
+	bool direct;        // avir_direct: the caller's image IS the float result
+	const float* fsrc;  // the float source, its pitch, ...
 	long fstride;
-	bool need_pack, packed;
+	bool packed;        // ... and whether the pack pass has run for this call
+	float* fdst;
 };
 
-static int avir_pack( avirhip_plan* p, AvirSrc& S, int row0, int row1,
-	hipStream_t st )
+static bool dtype_is_int( const int t )
 {
-	if( !S.need_pack || S.packed )
+	return( t == AVIRHIP_U8 || t == AVIRHIP_U16 );
+}
+
+// (AVIRHIP_VARIANT_UP2_UNFUSED_IO: the process-wide switch, per plan)
+static bool avir_fio( const AvirCall& C )
+{
+	return( fused_io() && !( C.path == 4 &&
+		( C.p -> variant & AVIRHIP_VARIANT_UP2_UNFUSED_IO )));
+}
+
+// integer / narrow output without gamma / error diffusion: the last pass
+// may convert and store into the caller's image itself (no float result,
+// no epilogue pass)
+// (half / bfloat16 pixels: the marching kernel (4) and the last pass of
+// the pass kernels (5, 1-4 channels: gp_store_int_row) narrow and store
+// them; behind the tiles the output stage does)
+static bool avir_stores( const AvirCall& C )
+{
+	const avirhip_plan* const p = C.p;
+
+	return( !C.direct && !p -> gamma &&
+		(( p -> dither == AVIRHIP_DITHER_DEF && dtype_is_int( p -> out_type )) ||
+		p -> out_type == AVIRHIP_F32 ||
+		( dtype_is_float16_kind( p -> out_type ) && ( C.path == 4 ||
+		( C.path == 5 && gpass_io16() )))) && avir_fio( C ));
+}
+
+// this result is the whole-ratio vertical kernel's to store (the two-pass
+// tiles, and k_dnfh's integer results): RGBA uint8 pixels are stored whole
+static bool avir_dn_stores( const AvirCall& C )
+{
+	return( avir_stores( C ) && !( C.p -> out_type == AVIRHIP_U8 &&
+		C.p -> io_ch == 4 && ( (uintptr_t) C.dst & 3 ) != 0 ) &&
+		fused_stores_int( C.p, C.path ));
+}
+
+// The store side of k_dnfh's sRGB kinds ALONE (a source the kernel cannot
+// read: the pack pass in front of k_dnfh< F32, S8 >) saves the output stage's
+// launch and the float result, and pays for the threshold search in the column
+// waves, which the DMA-fed row waves no longer hide: it is taken for frames of
+// up to dnsrgb_store_maxpix() source pixels (AVIRHIP_DNSRGB_STORE_MAXPIX, read
+// per call; measured in NOTEBOOK section 29).
+static long dnsrgb_store_maxpix()
+{
+	const char* const e = getenv( "AVIRHIP_DNSRGB_STORE_MAXPIX" );
+
+	return( e != nullptr ? atol( e ) : 1000000L );
+}
+
+// ---- the road of one call (avir_road): decided once, as data, before
+// anything is launched or allocated -- the attempts in the order they are
+// made. An attempt is a kernel family and its two sides. The source: RAW, the
+// first kernel reads the caller's image as it lies, or FLOAT, the caller's
+// float image or the pack pass's copy. The result: STORE, the last pass
+// converts and stores the caller's pixels at `dst`, or FLOAT, `dst` itself
+// when `direct`, else `resbuf` and the output stage. A family's launcher that
+// refuses the call (1: alignment, a source window, ...) hands it to the next
+// attempt. Per path, every row whose condition holds, in this order:
+//
+//   attempt        path   condition                                      launches
+//   k_dnfh sRGB    2      gamma, 8-bit pixels on a side the kernel may   k_dnfh
+//                         take: RAW uint8 RGBA at a base and pitch that
+//                         are multiples of 4 | STORE uint8; the store
+//                         side alone up to dnsrgb_store_maxpix() pixels
+//   k_dnfh 16-bit  2      no gamma, half / bfloat16 pixels on a side the k_dnfh
+//                         kernel may take: RAW 16-bit / float RGBA that
+//                         lanc2h_image_ok takes | STORE 16-bit at an even
+//                         base, integers as the tiles'
+//   tiles          2, 3   RAW integer pixels | STORE: avir_dn_stores     k_tile / k_dnf,
+//                                                                        dn passes
+//   k_up2 raw      4      RAW + STORE: integer RGB(A) or 16-bit RGBA on  k_up2
+//                         both sides, up2_stores_io
+//   k_up2 store    4      FLOAT + STORE: avir_stores                     k_up2
+//   k_up2          4      FLOAT + FLOAT                                  k_up2
+//   pass store     5      STORE: avir_stores; RAW as below               gpass_route's
+//   pass           5      RAW integer / float / 16-bit (`raw16`) pixels  gpass_route's
+//                         that gpass_takes_raw takes | FLOAT result
+//   generic        any    the automatic path (and every path but 2-5)    run_generic
+//
+// A forced path 2-5 has no generic attempt: when its last attempt refuses, the
+// call ends in AVIRHIP_EUNSUPPORTED (`forced`).
+//
+// `lazy`: the call skips ensure_scratch and allocates `packed` and `resbuf`
+// only when an attempt is about to use them -- k_dnfh's two roads, taken or
+// not, and the pass kernels with 16-bit pixels on a side. `first`: what the
+// tiles behind k_dnfh, refused or never listed, ask of the plan before they
+// make their sides ready: behind the sRGB kinds the float copies their road
+// expects to find (ensure_scratch), behind the 16-bit kinds `resbuf` -- also
+// where the tiles then store.
+enum AvirFamily { AVF_DNSRGB, AVF_DN16, AVF_TILES, AVF_UP2, AVF_GPASS,
+	AVF_GENERIC };
+enum AvirSide { AVS_FLOAT, AVS_RAW, AVS_STORE };
+enum AvirFirst { AV1_NOTHING, AV1_SCRATCH, AV1_RESBUF };
+
+struct AvirAttempt
+{
+	AvirFamily family;
+	AvirSide src, res;  // AVS_RAW | AVS_FLOAT, AVS_STORE | AVS_FLOAT
+	AvirFirst first;
+};
+
+struct AvirRoad
+{
+	int n;
+	AvirAttempt a[ 4 ];
+	bool lazy, forced;
+};
+
+static AvirRoad avir_road( const AvirCall& C )
+{
+	const avirhip_plan* const p = C.p;
+	const int path = C.path;
+	const bool int_in = dtype_is_int( p -> in_type );
+	const bool h_in = dtype_is_float16_kind( p -> in_type );
+	const bool h_out = dtype_is_float16_kind( p -> out_type );
+	const bool dn_fio = ( path == 2 && p -> ch == 4 && fused_io() &&
+		!( p -> variant & AVIRHIP_VARIANT_DN_UNFUSED_IO ));
+	AvirFirst tiles_first = AV1_NOTHING;
+	AvirRoad R;
+
+	R.n = 0;
+	R.forced = ( p -> path != 0 && path >= 2 && path <= 5 );
+
+	auto add = [&R]( const AvirFamily f, const bool raw, const bool store,
+		const AvirFirst first )
+	{
+		R.a[ R.n++ ] = AvirAttempt{ f, ( raw ? AVS_RAW : AVS_FLOAT ),
+			( store ? AVS_STORE : AVS_FLOAT ), first };
+	};
+
+	// Whole-ratio downsizing on both axes (path 2) WITH sRGB gamma and 8-bit
+	// pixels on a side: k_dnfh's DH_S8 kinds -- one launch that linearises a
+	// uint8 RGBA source where it lies (the plan's table) and de-linearises and
+	// stores a uint8 result itself (the plan's thresholds; the default
+	// ditherer). The sides are independent: `s8` / `o8` say which of them the
+	// kernel may take. AVIRHIP_VARIANT_DN_UNFUSED_IO: the tiles' road (pack
+	// pass, k_dnf, output stage).
+	const bool s8 = ( p -> in_type == AVIRHIP_U8 && p -> io_ch == 4 );
+	const bool o8 = ( p -> out_type == AVIRHIP_U8 &&
+		p -> dither == AVIRHIP_DITHER_DEF && p -> d_gthr != nullptr );
+	const bool srgb = ( dn_fio && p -> gamma && !p -> fp4 && !p -> f64 &&
+		( s8 || o8 ) && fused_dn16( p ));
+
+	if( srgb )
+	{
+		// A source the kernel refuses (a base or a pitch that is no multiple
+		// of 4 bytes) or cannot read (RGB, uint16, float) goes through the
+		// pack pass's linear copy; a result it cannot store goes as linear
+		// float rows. Neither side the kernel's after all: the tiles
+		const bool src_own = ( s8 && ( (uintptr_t) C.img.ptr & 3 ) == 0 &&
+			( p -> src_stride & 3 ) == 0 );
+
+		if( src_own || ( o8 &&
+			(long) p -> src_w * p -> src_h <= dnsrgb_store_maxpix() ))
+		{
+			add( AVF_DNSRGB, src_own, o8, AV1_NOTHING );
+		}
+
+		tiles_first = AV1_SCRATCH;
+	}
+
+	// ... with half / bfloat16 pixels on a side, no gamma, the default
+	// ditherer: one launch that reads a 16-bit RGBA source where it lies and
+	// narrows and stores a 16-bit result itself
+	const bool dn16 = ( dn_fio && !p -> gamma &&
+		p -> dither == AVIRHIP_DITHER_DEF && ( h_in || h_out ) &&
+		fused_dn16( p ));
+
+	if( dn16 )
+	{
+		// the source k_dnfh reads: the caller's half / bfloat16 / float RGBA
+		// image where it lies, the pack pass's float copy of any other (and
+		// of one lanc2h_image_ok refuses: a misaligned base, an odd pitch)
+		const bool src_own = ( p -> io_ch == 4 && ( h_in || !C.need_pack ) &&
+			lanc2h_image_ok( C.img.ptr, p -> in_type, p -> src_stride ));
+		// the result: narrowed and stored by the kernel (half / bfloat16),
+		// through the integer output stage as k_dnf's, or float rows
+		const bool hout = ( !C.direct && ( h_out ?
+			( (uintptr_t) C.dst & 1 ) == 0 : avir_dn_stores( C )));
+
+		if(( src_own && p -> in_type != AVIRHIP_F32 ) || ( hout && h_out ))
+		{
+			add( AVF_DN16, src_own, hout, AV1_NOTHING );
+		}
+
+		tiles_first = AV1_RESBUF;
+	}
+
+	// (nor does a call of the pass kernels with 16-bit pixels on a side, whose
+	// first pass may read and whose last pass may store them, make its float
+	// copies up front)
+	R.lazy = ( srgb || dn16 || ( path == 5 && !p -> gamma && gpass_io16() &&
+		( h_in || h_out )));
+
+	// integer / narrower sources: the path's first kernel reads the caller's
+	// image as it lies, the float copy of the source (pack pass) is skipped --
+	// the tile loaders (2, 3), the streaming pass kernel (5), and the marching
+	// kernel (4) when it also stores the caller's integer pixels (it may still
+	// refuse the call -- alignment, a source window: the pack pass runs then)
+	const bool raw_ok = ( !p -> gamma && p -> ch == 4 );
+
+	if( path == 2 || path == 3 )
+	{
+		add( AVF_TILES, raw_ok && int_in && fused_takes_raw( p, path ),
+			avir_dn_stores( C ), tiles_first );
+	}
+
+	if( path == 4 )
+	{
+		// half RGBA on both sides, or bfloat16 RGBA on both sides: the marching
+		// kernel reads the elements as they lie
+		const bool half_io = ( h_in && p -> out_type == p -> in_type &&
+			p -> io_ch == 4 );
+		const bool stores = avir_stores( C );
+
+		if( stores && raw_ok && C.need_pack && (( int_in &&
+			( p -> io_ch == 3 || p -> io_ch == 4 ) &&
+			dtype_is_int( p -> out_type )) || half_io ) &&
+			p -> dither == AVIRHIP_DITHER_DEF && up2_stores_io( p ) &&
+			avir_fio( C ))
+		{
+			add( AVF_UP2, true, true, AV1_NOTHING ); // (no pack pass, no epilogue)
+		}
+
+		if( stores )
+		{
+			add( AVF_UP2, false, true, AV1_NOTHING );
+		}
+
+		add( AVF_UP2, false, false, AV1_NOTHING );
+	}
+
+	if( path == 5 )
+	{
+		// a half / bfloat16 source k_gh's typed loader takes: elements
+		// are loaded whole, four at a time -- a base that is a multiple of their
+		// size, at least four of them up to the end of the last source row the
+		// band's first pass reads (run_h's `raw_elems`); any row pitch. The
+		// accumulation kernels' typed loaders (a horizontal axis with k >= 2,
+		// gpass.hip: sa16_wanted, asked through gpass_takes_raw) take the same
+		const bool raw16 = ( gpass_io16() && h_in &&
+			( (uintptr_t) C.img.ptr & 1 ) == 0 && C.row1 > C.row0 &&
+			(long) gpass_last_src_row( p, C.row0, C.row1 ) * p -> src_stride +
+			(long) p -> src_w * p -> io_ch >= 4 );
+		const bool raw = ( raw_ok && C.need_pack &&
+			( int_in || p -> in_type == AVIRHIP_F32 || raw16 ) &&
+			gpass_takes_raw( p ));
+
+		if( avir_stores( C ))
+		{
+			add( AVF_GPASS, raw, true, AV1_NOTHING );
+		}
+
+		// (this plan's last pass cannot: float result)
+		add( AVF_GPASS, raw, false, AV1_NOTHING );
+	}
+
+	if( !R.forced )
+	{
+		add( AVF_GENERIC, false, false, AV1_NOTHING );
+	}
+
+	return( R );
+}
+
+// The pack pass, at most once per call
+static int avir_pack( AvirCall& C )
+{
+	avirhip_plan* const p = C.p;
+
+	if( !C.need_pack || C.packed )
 	{
 		return( AVIRHIP_OK );
 	}
 
-	S.packed = true;
+	C.packed = true;
 
-	// (the road of avir_dn16 comes here without ensure_scratch -- its refused
-	// calls and exec_avir's generic fall-back behind it; a no-op elsewhere)
+	// (a lazy call comes here without ensure_scratch; a no-op elsewhere)
 	const int ra = need_floats( p, &p -> packed, (size_t) p -> src_w *
 		p -> src_h * p -> ch );
 
 	if( ra != 0 ) return( ra );
-	S.f = p -> packed;
+	C.fsrc = p -> packed;
 
 	// a band converts the source rows its windows read, nothing else (the
 	// pipelined host-pointer call is 16 bands: 16 whole-frame packs otherwise)
 	int pa, pb;
-	band_src_rows( p, row0, row1, &pa, &pb );
+	band_src_rows( p, C.row0, C.row1, &pa, &pb );
 
 	if( pb < pa )
 	{
 		return( AVIRHIP_OK );
 	}
 
-	const char* const ps = (const char*) S.img + (size_t) pa *
+	const char* const ps = (const char*) C.img.ptr + (size_t) pa *
 		p -> src_stride * dtype_size( p -> in_type );
 	float* const pd = p -> packed + (size_t) pa * p -> src_w * p -> ch;
 	verbose_stage( "pack pass", pb - pa + 1 );
@@ -1156,220 +1452,75 @@ static int avir_pack( avirhip_plan* p, AvirSrc& S, int row0, int row1,
 	{
 		return( launch_pack_gamma( ps, p -> in_type, pd, p -> src_w,
 			pb - pa + 1, p -> io_ch, p -> ch, p -> src_stride,
-			p -> alpha_index, p -> d_srgb_tbl, st ));
+			p -> alpha_index, p -> d_srgb_tbl, C.st ));
 	}
 
 	return( launch_pack( ps, p -> in_type, pd, p -> src_w, pb - pa + 1,
-		p -> io_ch, p -> ch, p -> src_stride, st ));
-}
-
-// Whole-ratio downsizing on both axes (path 2) with half / bfloat16 pixels on a
-// side, no gamma, the default ditherer: k_dnfh's road (avir_fast) -- one launch
-// that reads a 16-bit RGBA source where it lies and narrows and stores a 16-bit
-// result itself. Such a call allocates `packed` and `resbuf` only when
-// something is about to use them. AVIRHIP_VARIANT_DN_UNFUSED_IO: today's road
-// (pack pass, k_dnf, output stage).
-static bool avir_dn16( const avirhip_plan* p, const int path )
-{
-	return( path == 2 && !p -> gamma && p -> ch == 4 &&
-		p -> dither == AVIRHIP_DITHER_DEF && fused_io() &&
-		( dtype_is_float16_kind( p -> in_type ) ||
-		dtype_is_float16_kind( p -> out_type )) &&
-		!( p -> variant & AVIRHIP_VARIANT_DN_UNFUSED_IO ) && fused_dn16( p ));
+		p -> io_ch, p -> ch, p -> src_stride, C.st ));
 }
 
 // the float result buffer of a call that is not `direct`, when it is needed
-static int avir_need_res( avirhip_plan* p, float*& fdst, const bool direct )
+static int avir_need_res( const AvirCall& C )
 {
-	if( direct )
-	{
-		return( AVIRHIP_OK );
-	}
-
-	const int rc = need_floats( p, &p -> resbuf, (size_t) p -> new_w *
-		p -> new_h * p -> ch );
-
-	fdst = p -> resbuf;
-	return( rc );
+	return( C.direct ? AVIRHIP_OK : need_floats( C.p, &C.p -> resbuf,
+		(size_t) C.p -> new_w * C.p -> new_h * C.p -> ch ));
 }
 
-// The fast paths of an AVIR call: 5 (pass kernels), 4 (exact-2x marching
-// kernel), 2 / 3 (LDS tiles). Returns 1 when the path cannot take the call
-// (the generic chain does), 0 when it ran: `stored` -- its last pass converted
-// and stored the caller's pixels at `dst`; otherwise the float result is at
-// `fdst`. `direct`: the caller's image IS the float result (fdst == dst).
-static int avir_fast( avirhip_plan* p, const int path, AvirSrc& S, void* dst,
-	float*& fdst, const bool direct, int row0, int row1, hipStream_t st,
-	const SrcWindow win, bool& stored )
+// ---- one function per family: its launcher, with the sides of the attempt.
+// Each returns the launcher's code -- 1: it cannot take this call.
+static int avir_run_dnfh( AvirCall& C, const AvirAttempt& A )
 {
-	int rc;
-	const ImageRef img = { S.img, p -> in_type, p -> io_ch, p -> src_stride };
-	const bool int_in = ( p -> in_type == AVIRHIP_U8 ||
-		p -> in_type == AVIRHIP_U16 );
-	const bool int_out = ( p -> out_type == AVIRHIP_U8 ||
-		p -> out_type == AVIRHIP_U16 );
-	// (AVIRHIP_VARIANT_UP2_UNFUSED_IO: the process-wide switch, per plan)
-	const bool fio = ( fused_io() && !( path == 4 &&
-		( p -> variant & AVIRHIP_VARIANT_UP2_UNFUSED_IO )));
+	const ImageRef hsrc = ( A.src == AVS_RAW ? C.img : ImageRef{ C.fsrc,
+		AVIRHIP_F32, 4, C.fstride });
+	void* const hout = ( A.res == AVS_STORE ? C.dst : nullptr );
 
-	// integer / narrow output without gamma / error diffusion: the last pass
-	// may convert and store into the caller's image itself (no float result,
-	// no epilogue pass)
-	// (half / bfloat16 pixels: the marching kernel (4) and the last pass of
-	// the pass kernels (5, 1-4 channels: gp_store_int_row) narrow and store
-	// them; behind the tiles the output stage does)
-	const bool io16 = ( path == 5 && gpass_io16() );
-	const bool stores = ( !direct && !p -> gamma &&
-		(( p -> dither == AVIRHIP_DITHER_DEF && int_out ) ||
-		p -> out_type == AVIRHIP_F32 ||
-		( dtype_is_float16_kind( p -> out_type ) && ( path == 4 || io16 ))) &&
-		fio );
-	// a half / bfloat16 source k_gh's typed loader takes (path 5): elements
-	// are loaded whole, four at a time -- a base that is a multiple of their
-	// size, at least four of them up to the end of the last source row the
-	// band's first pass reads (run_h's `raw_elems`); any row pitch. The
-	// accumulation kernels' typed loaders (a horizontal axis with k >= 2,
-	// gpass.hip: sa16_wanted, asked through gpass_takes_raw) take the same
-	const bool raw16 = ( io16 && dtype_is_float16_kind( p -> in_type ) &&
-		( (uintptr_t) S.img & 1 ) == 0 && row1 > row0 &&
-		(long) gpass_last_src_row( p, row0, row1 ) * p -> src_stride +
-		(long) p -> src_w * p -> io_ch >= 4 );
-	// half RGBA on both sides, or bfloat16 RGBA on both sides: the marching
-	// kernel reads the elements as they lie
-	const bool half_io = ( dtype_is_float16_kind( p -> in_type ) &&
-		p -> out_type == p -> in_type && p -> io_ch == 4 );
+	return( A.family == AVF_DNSRGB ?
+		fused_run_dnsrgb( C.p, hsrc, C.fdst, C.row0, C.row1, C.st, hout ) :
+		fused_run_dn16( C.p, hsrc, C.fdst, C.row0, C.row1, C.st, hout ));
+}
 
-	// integer / narrower sources: the path's first kernel reads the caller's
-	// image as it lies, the float copy of the source (pack pass) is skipped --
-	// the tile loaders (2, 3), the streaming pass kernel (5), and the marching
-	// kernel (4) when it also stores the caller's integer pixels (it may still
-	// refuse the call -- alignment, a source window: the pack pass runs then)
-	const bool raw = ( !p -> gamma && p -> ch == 4 && ( path == 5 ?
-		S.need_pack && ( int_in || p -> in_type == AVIRHIP_F32 || raw16 ) &&
-		gpass_takes_raw( p ) :
-		path == 4 ? S.need_pack && (( int_in &&
-		( p -> io_ch == 3 || p -> io_ch == 4 ) && int_out ) || half_io ) &&
-		p -> dither == AVIRHIP_DITHER_DEF && up2_stores_io( p ) && fio :
-		int_in && fused_takes_raw( p, path )));
+static int avir_run_tiles( AvirCall& C, const AvirAttempt& A )
+{
+	avirhip_plan* const p = C.p;
+	void* const iout = ( A.res == AVS_STORE ? C.dst : nullptr );
 
-	stored = false;
+	return( A.src == AVS_RAW ?
+		fused_run( p, C.path, C.img.ptr, p -> in_type, p -> io_ch,
+		p -> src_stride, C.fdst, C.row0, C.row1, C.st, iout ) :
+		fused_run( p, C.path, C.fsrc, AVIRHIP_F32, 4, C.fstride, C.fdst,
+		C.row0, C.row1, C.st, iout ));
+}
 
-	if( avir_dn16( p, path ))
+static int avir_run_up2( AvirCall& C, const AvirAttempt& A )
+{
+	if( A.res == AVS_STORE )
 	{
-		// the source k_dnfh reads: the caller's half / bfloat16 / float RGBA
-		// image where it lies, the pack pass's float copy of any other (and
-		// of one lanc2h_image_ok refuses: a misaligned base, an odd pitch)
-		const bool h_out = dtype_is_float16_kind( p -> out_type );
-		const bool src_own = ( p -> io_ch == 4 &&
-			( dtype_is_float16_kind( p -> in_type ) || !S.need_pack ) &&
-			lanc2h_image_ok( S.img, p -> in_type, p -> src_stride ));
-		// the result: narrowed and stored by the kernel (half / bfloat16),
-		// through the integer output stage as k_dnf's, or float rows
-		void* const hout = ( direct ? nullptr : h_out ?
-			(( (uintptr_t) dst & 1 ) == 0 ? dst : nullptr ) :
-			( stores && !( p -> out_type == AVIRHIP_U8 && p -> io_ch == 4 &&
-			( (uintptr_t) dst & 3 ) != 0 ) && fused_stores_int( p, path ) ?
-			dst : nullptr ));
-
-		if(( src_own && p -> in_type != AVIRHIP_F32 ) ||
-			( hout != nullptr && h_out ))
-		{
-			if( !src_own && ( rc = avir_pack( p, S, row0, row1, st )) != 0 )
-				return( rc );
-
-			if( hout == nullptr &&
-				( rc = avir_need_res( p, fdst, direct )) != 0 ) return( rc );
-
-			const ImageRef hsrc = ( src_own ? img : ImageRef{ S.f,
-				AVIRHIP_F32, 4, S.fstride });
-
-			rc = fused_run_dn16( p, hsrc, fdst, row0, row1, st, hout );
-
-			if( rc != 1 )
-			{
-				stored = ( rc == 0 && hout != nullptr );
-				return( rc );
-			}
-		}
-
-		// (today's road: the float result, where the call has one)
-		if(( rc = avir_need_res( p, fdst, direct )) != 0 ) return( rc );
+		return( A.src == AVS_RAW ?
+			up2_run( C.p, nullptr, 0, nullptr, C.row0, C.row1, C.st, C.win,
+			&C.img, C.dst ) :
+			up2_run( C.p, C.fsrc, C.fstride, nullptr, C.row0, C.row1, C.st,
+			C.win, nullptr, C.dst ));
 	}
 
-	if( !raw && ( rc = avir_pack( p, S, row0, row1, st )) != 0 ) return( rc );
+	return( up2_run( C.p, C.fsrc, C.fstride, C.fdst, C.row0, C.row1, C.st,
+		C.win, nullptr, nullptr ));
+}
 
-	if( path == 5 )
-	{
-		void* iout = ( stores ? dst : nullptr );
+static int avir_run_gpass( AvirCall& C, const AvirAttempt& A )
+{
+	void* const iout = ( A.res == AVS_STORE ? C.dst : nullptr );
 
-		for( ;; )
-		{
-			// (calls with 16-bit pixels come without ensure_scratch, exec_avir:
-			// the float result is made when a pass is about to write it)
-			if( iout == nullptr &&
-				( rc = avir_need_res( p, fdst, direct )) != 0 ) return( rc );
+	return( A.src == AVS_RAW ?
+		gpass_run( C.p, nullptr, 0, C.fdst, C.row0, C.row1, C.st, &C.img, iout,
+		nullptr ) :
+		gpass_run( C.p, C.fsrc, C.fstride, C.fdst, C.row0, C.row1, C.st,
+		nullptr, iout, nullptr ));
+}
 
-			rc = ( raw ?
-				gpass_run( p, nullptr, 0, fdst, row0, row1, st, &img, iout,
-				nullptr ) :
-				gpass_run( p, S.f, S.fstride, fdst, row0, row1, st, nullptr,
-				iout, nullptr ));
-
-			if( rc != 1 || iout == nullptr )
-			{
-				stored = ( rc == 0 && iout != nullptr );
-				return( rc );
-			}
-
-			iout = nullptr; // this plan's last pass cannot: float result
-		}
-	}
-
-	if( path == 4 )
-	{
-		if( stores && raw )
-		{
-			rc = up2_run( p, nullptr, 0, nullptr, row0, row1, st, win, &img,
-				dst );
-
-			if( rc != 1 )
-			{
-				stored = ( rc == 0 ); // (no pack pass, no epilogue)
-				return( rc );
-			}
-		}
-
-		if(( rc = avir_pack( p, S, row0, row1, st )) != 0 ) return( rc );
-
-		if( stores )
-		{
-			rc = up2_run( p, S.f, S.fstride, nullptr, row0, row1, st, win,
-				nullptr, dst );
-
-			if( rc != 1 )
-			{
-				stored = ( rc == 0 );
-				return( rc );
-			}
-		}
-
-		return( up2_run( p, S.f, S.fstride, fdst, row0, row1, st, win,
-			nullptr, nullptr ));
-	}
-
-	// the tiles: the whole-ratio vertical kernel of the two-pass path stores
-	void* const iout = ( stores && !( p -> out_type == AVIRHIP_U8 &&
-		p -> io_ch == 4 && ( (uintptr_t) dst & 3 ) != 0 ) &&
-		fused_stores_int( p, path ) ? dst : nullptr );
-
-	rc = ( raw ?
-		fused_run( p, path, S.img, p -> in_type, p -> io_ch, p -> src_stride,
-		fdst, row0, row1, st, iout ) :
-		fused_run( p, path, S.f, AVIRHIP_F32, 4, S.fstride, fdst, row0, row1,
-		st, iout ));
-
-	stored = ( rc == 0 && iout != nullptr );
-	return( rc );
+static int avir_run_generic( AvirCall& C, const AvirAttempt& )
+{
+	return( run_generic( C.p, C.fsrc, C.fstride, C.fdst, C.row0, C.row1,
+		C.st ));
 }
 
 // The tail of an AVIR call whose float result is at `fdst` (and is not the
@@ -1409,170 +1560,77 @@ static int avir_output( avirhip_plan* p, const float* fdst, void* dst,
 		p -> d_gthr, ( p -> dither == AVIRHIP_DITHER_DEF_RNE )));
 }
 
-// Whole-ratio downsizing on both axes (path 2) WITH sRGB gamma and 8-bit pixels
-// on a side: k_dnfh's DH_S8 kinds -- one launch that linearises a uint8 RGBA
-// source where it lies (the plan's table) and de-linearises and stores a uint8
-// result itself (the plan's thresholds; the default ditherer). The sides are
-// independent: `s8` / `o8` say which of them the kernel may take.
-// AVIRHIP_VARIANT_DN_UNFUSED_IO: today's road (pack pass, k_dnf, output stage).
-//
-// The store side ALONE (a source the kernel cannot read: the pack pass in
-// front of k_dnfh< F32, S8 >) saves the output stage's launch and the float
-// result, and pays for the threshold search in the column waves, which the
-// DMA-fed row waves no longer hide: it is taken for frames of up to
-// dnsrgb_store_maxpix() source pixels (AVIRHIP_DNSRGB_STORE_MAXPIX, read per
-// call; measured in NOTEBOOK section 29).
-static long dnsrgb_store_maxpix()
+// The attempts of a road in turn, each with its sides made ready, until one
+// does not refuse the call; then the output stage, unless the last pass stored
+// the caller's pixels or the caller's image is the float result.
+static int avir_execute( AvirCall& C, const AvirRoad& R )
 {
-	const char* const e = getenv( "AVIRHIP_DNSRGB_STORE_MAXPIX" );
+	static int ( * const run[] )( AvirCall&, const AvirAttempt& ) = {
+		avir_run_dnfh, avir_run_dnfh, avir_run_tiles, avir_run_up2,
+		avir_run_gpass, avir_run_generic }; // (by AvirFamily)
+	avirhip_plan* const p = C.p;
+	bool stored = false;
+	int rc = 1;
 
-	return( e != nullptr ? atol( e ) : 1000000L );
-}
-
-static bool avir_dnsrgb( const avirhip_plan* p, const int path, bool& s8,
-	bool& o8 )
-{
-	s8 = ( p -> in_type == AVIRHIP_U8 && p -> io_ch == 4 );
-	o8 = ( p -> out_type == AVIRHIP_U8 && p -> dither == AVIRHIP_DITHER_DEF &&
-		p -> d_gthr != nullptr );
-
-	return( path == 2 && p -> gamma && !p -> fp4 && !p -> f64 && p -> ch == 4 &&
-		fused_io() && !( p -> variant & AVIRHIP_VARIANT_DN_UNFUSED_IO ) &&
-		( s8 || o8 ) && fused_dn16( p ));
-}
-
-// The call of that road. A source the kernel refuses (a base or a pitch that
-// is no multiple of 4 bytes) or cannot read (RGB, uint16, float) goes through
-// the pack pass's linear copy; a result it cannot store goes as linear float
-// rows to `fdst` (the caller's float RGBA image, or `resbuf` and the output
-// stage). Returns 1 when neither side is the kernel's after all, or its
-// launcher refuses: today's road; 0: `stored` as avir_fast's.
-static int avir_dnsrgb_run( avirhip_plan* p, const bool s8, const bool o8,
-	AvirSrc& S, void* dst, float*& fdst, const bool direct, int row0, int row1,
-	hipStream_t st, bool& stored )
-{
-	int rc;
-	const bool src_own = ( s8 && ( (uintptr_t) S.img & 3 ) == 0 &&
-		( p -> src_stride & 3 ) == 0 );
-
-	stored = false;
-
-	if( !src_own && ( !o8 ||
-		(long) p -> src_w * p -> src_h > dnsrgb_store_maxpix() ))
+	for( int i = 0; i < R.n && rc == 1; i++ )
 	{
-		return( 1 );
+		const AvirAttempt& A = R.a[ i ];
+
+		if( A.first == AV1_SCRATCH && ( rc = ensure_scratch( p )) != 0 )
+			return( rc );
+
+		if( A.first == AV1_RESBUF && ( rc = avir_need_res( C )) != 0 )
+			return( rc );
+
+		if( A.src == AVS_FLOAT && ( rc = avir_pack( C )) != 0 ) return( rc );
+		if( A.res == AVS_FLOAT && ( rc = avir_need_res( C )) != 0 ) return( rc );
+
+		C.fdst = ( C.direct ? (float*) C.dst : p -> resbuf );
+		rc = run[ A.family ]( C, A );
+		stored = ( rc == 0 && A.res == AVS_STORE );
 	}
 
-	if( !src_own && ( rc = avir_pack( p, S, row0, row1, st )) != 0 )
-		return( rc );
+	if( rc == 1 && R.forced )
+	{
+		set_error( "path %d cannot run this call (unaligned buffers?)",
+			C.path );
+		return( AVIRHIP_EUNSUPPORTED );
+	}
 
-	if( !o8 && ( rc = avir_need_res( p, fdst, direct )) != 0 ) return( rc );
+	if( rc != 0 || stored || C.direct )
+	{
+		return( rc ); // (no epilogue)
+	}
 
-	const ImageRef hsrc = ( src_own ? ImageRef{ S.img, AVIRHIP_U8, 4,
-		p -> src_stride } : ImageRef{ S.f, AVIRHIP_F32, 4, S.fstride });
-
-	rc = fused_run_dnsrgb( p, hsrc, fdst, row0, row1, st,
-		( o8 ? dst : nullptr ));
-
-	stored = ( rc == 0 && o8 );
-	return( rc );
+	return( avir_output( p, C.fdst, C.dst, C.row0, C.row1, C.st ));
 }
 
 static int exec_avir( avirhip_plan* p, const void* src, void* dst, int row0,
 	int row1, hipStream_t st, const SrcWindow win )
 {
-	const int path = ( p -> path != 0 ? p -> path : p -> auto_path );
-	// (k_dnfh's road makes neither float copy: avir_pack and avir_need_res
-	// allocate them where a refused call needs them after all)
-	// (nor does a call of the pass kernels with 16-bit pixels on a side, whose
-	// first pass may read and whose last pass may store them: avir_fast)
-	const bool gp16 = ( path == 5 && !p -> gamma && gpass_io16() &&
-		( dtype_is_float16_kind( p -> in_type ) ||
-		dtype_is_float16_kind( p -> out_type )));
-	// (nor does k_dnfh's road with gamma: avir_dnsrgb)
-	bool s8, o8;
-	const bool srgb = avir_dnsrgb( p, path, s8, o8 );
-	int rc = ( avir_dn16( p, path ) || gp16 || srgb ? AVIRHIP_OK :
-		ensure_scratch( p ));
-	if( rc != 0 ) return( rc );
+	AvirCall C;
+	C.p = p;
+	C.path = ( p -> path != 0 ? p -> path : p -> auto_path );
+	C.img = ImageRef{ src, p -> in_type, p -> io_ch, p -> src_stride };
+	C.dst = dst;
+	C.row0 = row0; C.row1 = row1;
+	C.st = st;
+	C.win = win;
+	C.need_pack = avir_need_pack( p );
+	C.direct = avir_direct( p );
+	C.fsrc = ( C.need_pack ? nullptr : (const float*) src );
+	C.fstride = ( C.need_pack ? (long) p -> src_w * p -> ch :
+		(long) p -> src_stride );
+	C.packed = false;
+	C.fdst = nullptr;
 
-	const bool need_pack = ( p -> gamma || p -> in_type != AVIRHIP_F32 ||
-		p -> ch != p -> io_ch );
-	AvirSrc S = { src, ( need_pack ? p -> packed : (const float*) src ),
-		( need_pack ? (long) p -> src_w * p -> ch : (long) p -> src_stride ),
-		need_pack, false };
+	const AvirRoad R = avir_road( C );
 
-	// float output is the vertical pass' in-place result (avir.h:4956-4979):
-	// with gamma it stays linear, only the other output types are
-	// de-linearised in the epilogue
-	// (fpclass_float4 has no in-place output: its float results pass through
-	// the output stage like every other type, which matters with gamma)
-	const bool direct = ( p -> out_type == AVIRHIP_F32 &&
-		p -> ch == p -> io_ch && !( p -> fp4 && p -> gamma ));
-	float* fdst = ( direct ? (float*) dst : p -> resbuf );
+	// (a lazy road makes neither float copy: avir_pack and avir_need_res
+	// allocate them where an attempt needs them after all)
+	const int rc = ( R.lazy ? AVIRHIP_OK : ensure_scratch( p ));
 
-	if( srgb )
-	{
-		bool stored = false;
-		rc = avir_dnsrgb_run( p, s8, o8, S, dst, fdst, direct, row0, row1, st,
-			stored );
-
-		if( rc == 0 )
-		{
-			return( stored || direct ? AVIRHIP_OK :
-				avir_output( p, fdst, dst, row0, row1, st ));
-		}
-
-		if( rc != 1 )
-		{
-			return( rc );
-		}
-
-		// today's road, with the float copies it expects to find
-		if(( rc = ensure_scratch( p )) != 0 ) return( rc );
-
-		if( need_pack )
-		{
-			S.f = p -> packed;
-		}
-
-		fdst = ( direct ? (float*) dst : p -> resbuf );
-	}
-
-	rc = 1;
-
-	if( path >= 2 && path <= 5 )
-	{
-		bool stored = false;
-		rc = avir_fast( p, path, S, dst, fdst, direct, row0, row1, st, win,
-			stored );
-
-		if( rc == 0 && stored )
-		{
-			return( AVIRHIP_OK ); // (no epilogue)
-		}
-
-		if( rc == 1 && p -> path != 0 )
-		{
-			set_error( "path %d cannot run this call (unaligned buffers?)",
-				path );
-			return( AVIRHIP_EUNSUPPORTED );
-		}
-	}
-
-	if( rc == 1 )
-	{
-		if(( rc = avir_pack( p, S, row0, row1, st )) != 0 ) return( rc );
-		if(( rc = avir_need_res( p, fdst, direct )) != 0 ) return( rc );
-		rc = run_generic( p, S.f, S.fstride, fdst, row0, row1, st );
-	}
-
-	if( rc != 0 || direct )
-	{
-		return( rc );
-	}
-
-	return( avir_output( p, fdst, dst, row0, row1, st ));
+	return( rc != 0 ? rc : avir_execute( C, R ));
 }
 
 // One call on device-resident buffers, by route.

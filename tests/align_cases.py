@@ -140,7 +140,7 @@ FU_DST = _side(16, "fused.hip:1058", "if( (uintptr_t) dst & 15 )", REFUSED,
                "refused")
 Q_FU_U16 = "( src_type == AVIRHIP_U16 && ( (uintptr_t) src & 1 )))"
 Q_FU_RAW = "!fused_takes_raw( p, mode ) ||"
-Q_TILE_OUT = "p -> io_ch == 4 && ( (uintptr_t) dst & 3 ) != 0 ) &&"
+Q_TILE_OUT = "C.p -> io_ch == 4 && ( (uintptr_t) C.dst & 3 ) != 0 ) &&"
 Q_EPI = "if( !rne && ech == 4 && !gamma && ( (uintptr_t) dst & 3 ) == 0 )"
 
 Q_LF = "return( img.ptr != nullptr && ( (uintptr_t) img.ptr & 3 ) == 0 &&"
@@ -173,7 +173,7 @@ N_L2_RAW = ("the raw loader reads the aligned word that holds a lane's RGBA "
             "pixel (2 bytes for uint8 pairs, a dword for uint16) or, for RGB, "
             "single elements; the integer stage behind a raw RGBA source "
             "stores a lane's two elements at once at their own alignment "
-            "(dst2, api.cpp:962-967) and single elements otherwise: every "
+            "(dst2, api.cpp:979-984) and single elements otherwise: every "
             "access is whole elements of one row")
 N_GP = ("float RGBA pixels travel as 16-byte LDS-DMA pieces and leave as "
         "16-byte stores: with a 16-byte base and pitch every piece is one "
@@ -330,8 +330,8 @@ for _n, _t, _b in (("u8c4", "u8", 8), ("u16c4", "u16", 16)):
     _row("dnf_f32_" + _n, ["dnf.hip", "fused.hip"], "avir", DN2,
          dict(ch=4, tin="f32", tout=_t, bits=_b), 2, 0, "k_dnf",
          _s(FU_SRC, FU_PITCH,
-            _side(4, "api.cpp:1362", Q_TILE_OUT, OUT, "out") if _t == "u8"
-            else _elem(2, "api.cpp:1362", Q_TILE_OUT)), N_DN)
+            _side(4, "api.cpp:1184", Q_TILE_OUT, OUT, "out") if _t == "u8"
+            else _elem(2, "api.cpp:1184", Q_TILE_OUT)), N_DN)
 _row("dn_two_pass_f32", ["dn.hip"], "avir", DN2, F32R, 2,
      V.VARIANT_DN_TWO_PASS, "k_dnv", _s(FU_SRC, FU_PITCH, FU_DST), N_DN)
 for _n, _f, _g2 in (("u8c3", U8C3, (602, 400, 301, 200)), ("u8c4", U8C4, None),
@@ -341,8 +341,8 @@ for _n, _f, _g2 in (("u8c3", U8C3, (602, 400, 301, 200)), ("u8c4", U8C4, None),
          V.VARIANT_DN_TWO_PASS, "k_dnv",
          _s(_elem(_e, "fused.hip:1046", Q_FU_U16),
             _elem(_e, "fused.hip:1045", Q_FU_RAW),
-            _side(4, "api.cpp:1362", Q_TILE_OUT, OUT, "out")
-            if _n == "u8c4" else _elem(_e, "api.cpp:1362", Q_TILE_OUT)),
+            _side(4, "api.cpp:1184", Q_TILE_OUT, OUT, "out")
+            if _n == "u8c4" else _elem(_e, "api.cpp:1184", Q_TILE_OUT)),
          N_DN, geom2=_g2)
 # ---- k_up2
 _row("up2_f32", ["up2.hip"], "avir", X2, F32R, 4, 0, "k_up2",
@@ -452,18 +452,18 @@ _row("lanc2_f32", ["lanc2.hip"], "lancir", LX2, F32R, 4, 0, "k_lanc2",
      window=True)
 _row("lanc2_raw_u8c3", ["lanc2.hip"], "lancir", LX2, U8C3, 4, 0, "k_lanc2",
      _s(_elem(1, "lanc2.hip:543", Q_L2_RAW), _elem(1, "lanc2.hip:542", Q_L2_RAWP),
-        _elem(1, "api.cpp:964", Q_DST2_U8), _elem(1, "api.cpp:962", Q_DST2_P)),
+        _elem(1, "api.cpp:981", Q_DST2_U8), _elem(1, "api.cpp:979", Q_DST2_P)),
      N_L2_RAW, geom2=(161, 120, 322, 240))
 _row("lanc2_raw_u8c4", ["lanc2.hip"], "lancir", LX2, U8C4, 4, 0, "k_lanc2",
      _s(_side(2, "lanc2.hip:543", Q_L2_RAW, PACK, "pack"),
         _side(2, "lanc2.hip:542", Q_L2_RAWP, PACK, "pack"),
-        _side(2, "api.cpp:964", Q_DST2_U8, PACK, "pack"),
-        _side(2, "api.cpp:962", Q_DST2_P, PACK, "pack")), N_L2_RAW)
+        _side(2, "api.cpp:981", Q_DST2_U8, PACK, "pack"),
+        _side(2, "api.cpp:979", Q_DST2_P, PACK, "pack")), N_L2_RAW)
 _row("lanc2_raw_u16c4", ["lanc2.hip"], "lancir", LX2, U16C4, 4, 0, "k_lanc2",
      _s(_side(4, "lanc2.hip:543", Q_L2_RAW, PACK, "pack"),
         _side(4, "lanc2.hip:542", Q_L2_RAWP, PACK, "pack"),
-        _side(4, "api.cpp:966", Q_DST2_U16, PACK, "pack"),
-        _side(4, "api.cpp:962", Q_DST2_P, PACK, "pack")), N_L2_RAW)
+        _side(4, "api.cpp:983", Q_DST2_U16, PACK, "pack"),
+        _side(4, "api.cpp:979", Q_DST2_P, PACK, "pack")), N_L2_RAW)
 # ---- 8-byte elements and the double pipeline
 _Q64 = "const long e = (long) y * src_stride + (long) x * CH;"
 _row("lanc_f64_pack", ["generic.hip"], "lancir", LX2,

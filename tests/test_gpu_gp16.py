@@ -277,7 +277,7 @@ def test_refused_images_take_the_pack_road(t):
 @pytest.mark.parametrize("t", ["f16", "bf16"])
 def test_images_under_four_elements(t):
     """Fewer than four elements up to the end of a band's last source row: the
-    loader's 8-byte load does not fit, so `raw16` (api.cpp) is false. The
+    loader's 8-byte load does not fit, so `raw16` (api.cpp, avir_road) is false. The
     planner gives sources this small another chain than the pass kernels'
     (tests/test_gp16_table.py), so forced path 5 refuses their plans at
     avirhip_plan_set_path and the automatic path runs them: rc == 0, the
