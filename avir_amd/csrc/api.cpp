@@ -616,8 +616,8 @@ static bool avir_direct( const avirhip_plan* p )
 
 // The float copies a call may need, allocated up front: every road but
 // k_dnfh's and the pass kernels' with half / bfloat16 pixels on a side
-// (avir_road: `lazy`) calls this first. Those skip it, and avir_pack (`packed`)
-// and avir_need_res (`resbuf`) allocate each when something is about to use it
+// (avir_road: `lazy`) calls this first. Those skip it, and road_pack (`packed`)
+// and road_need_res (`resbuf`) allocate each when something is about to use it
 // -- the same sizes as here, so after this function they are no-ops.
 static int ensure_scratch( avirhip_plan* p )
 {
@@ -853,99 +853,103 @@ static void verbose_stage( const char* const name, const int rows )
 	}
 }
 
-// ---- LANCIR ----
+// ---- the execute road: AVIR and LANCIR ----
 
-// A LANCIR plan's own kernels, fastest first: the exact-2x marching kernel,
-// the pass kernels, the generic kernels. `raw` / `lout`: the call of an inner
-// plan by its owner (lancir_owner) -- `src` and `dst` may then be null, and
-// AVIRHIP_NEED_SRC / AVIRHIP_NEED_DST ask the owner for them. `stored`: the
-// last pass ran `lout` and stored the owner's pixels; otherwise the float
-// result is at `dst`.
-static int lancir_kernels( avirhip_plan* p, const float* src, float* dst,
-	int row0, int row1, hipStream_t st, const SrcWindow win,
-	const ImageRef* raw, const LancirOut* lout, bool& stored )
+// What belongs to one call. `p` is the plan of the caller's images, `k` the
+// plan whose kernels run: `p` itself, or a LANCIR owner's inner float RGBA
+// plan. Two things change while the call runs, here and nowhere else. The
+// float image the kernels read: the caller's own (float pixels of `k`'s
+// channel count, no gamma), or the plan's `packed` copy, which the pack pass
+// fills at most once per call and only when a kernel is about to read it
+// (road_pack). The float result: the caller's image when `direct`, else the
+// plan's `resbuf` (LANCIR: `lres`) -- null until something asked for it.
+struct RoadCall
 {
-	const int lpath = ( p -> path != 0 ? p -> path : p -> auto_path );
-	int rc;
+	avirhip_plan* p;
+	avirhip_plan* k;
+	int path;           // of `k`
+	ImageRef img;       // the caller's source
+	void* dst;          // the caller's result
+	int row0, row1;
+	hipStream_t st;
+	SrcWindow win;
+	bool need_pack;     // avir_need_pack; LANCIR: an owner's call
+	bool direct;        // avir_direct, LANCIR's `k == p`: `dst` IS the float result
+	const float* fsrc;  // the float source, its pitch, ...
+	long fstride;
+	bool packed;        // ... and whether the pack pass has run for this call
+	float* fdst;
+};
 
-	stored = false;
+// A road's attempts: a kernel family and its two sides each (above avir_road)
+enum RoadFamily { AVF_DNSRGB, AVF_DN16, AVF_TILES, AVF_UP2, AVF_GPASS,
+	AVF_GENERIC, AVF_LANC2H, AVF_LANC2, AVF_LPASS, AVF_LGENERIC };
+enum RoadSide { AVS_FLOAT, AVS_RAW, AVS_STORE };
+enum RoadFirst { AV1_NOTHING, AV1_SCRATCH, AV1_RESBUF };
 
-	if( lpath == 4 )
-	{
-		if( dst == nullptr && lout == nullptr )
-		{
-			return( AVIRHIP_NEED_DST );
-		}
-
-		rc = lanc2_run( p, src, dst, row0, row1, st, win, raw, lout );
-
-		if( rc != 1 )
-		{
-			stored = ( rc == 0 && lout != nullptr );
-			return( rc );
-		}
-
-		if( raw != nullptr )
-		{
-			// (the kernels below would read the float copy the owner skipped)
-			return( AVIRHIP_NEED_SRC );
-		}
-
-		if( p -> path != 0 )
-		{
-			set_error( "path 4 cannot run this call (unaligned buffers?)" );
-			return( AVIRHIP_EUNSUPPORTED );
-		}
-	}
-
-	if( lpath == 5 || ( lpath == 4 && p -> path == 0 && gpass_ok( p )))
-	{
-		// general-ratio pass kernels (vertical pass first)
-		rc = gpass_run( p, src, p -> src_stride, dst, row0, row1, st, raw,
-			nullptr, lout );
-
-		if( rc != 1 )
-		{
-			stored = ( rc == 0 && lout != nullptr );
-			return( rc );
-		}
-
-		if( p -> path != 0 )
-		{
-			set_error( "path 5 cannot run this call (unaligned buffers?)" );
-			return( AVIRHIP_EUNSUPPORTED );
-		}
-	}
-
-	if( dst == nullptr )
-	{
-		return( AVIRHIP_NEED_DST );
-	}
-
-	// (the generic kernels' intermediate is only allocated when they run)
-	if(( rc = ensure_scratch( p )) != 0 ) return( rc );
-
-	return( launch_lancir_generic( p, src, dst, p -> resbuf, row0, row1, st ));
-}
-
-// A LANCIR plan with integer / scaled / 1-3 channel pixels (the owner): its
-// inner float RGBA plan's kernels between a pack pass and the output stage.
-// Where the inner kernels can, the first reads the owner's image as it lies
-// and the last stores the owner's pixels: the float RGBA copy of the source
-// (`packed`) and the float result (`lres`) are only allocated when a pass asks
-// for them -- 16 bytes per source and per destination pixel, per plan, spare
-// and replica, that also count against the plan cache. With the automatic path
-// of uint8 / uint16 images neither is touched.
-static int lancir_owner( avirhip_plan* p, const void* src, void* dst,
-	int row0, int row1, hipStream_t st )
+struct RoadAttempt
 {
-	avirhip_plan* const q = p -> inner;
-	int rc;
+	RoadFamily family;
+	RoadSide src, res;  // AVS_RAW | AVS_FLOAT, AVS_STORE | AVS_FLOAT
+	RoadFirst first;
+};
 
-	if( row1 <= row0 )
+struct Road
+{
+	int n;
+	RoadAttempt a[ 5 ];
+	bool lazy, forced;
+};
+
+// ---- the road of one LANCIR call (lanc_road). A plain float RGBA plan, unity
+// gain, runs its own kernels on the caller's images: every side is FLOAT,
+// `direct`, no pack pass; so does any plan forced to path 1, whatever its
+// pixels. A plan with integer / scaled / 1-3 channel pixels (the owner) runs
+// its inner float RGBA plan's kernels between the pack pass and the output
+// stage; where they can, the first reads the owner's image as it lies (RAW)
+// and the last runs the owner's output stage in its store (STORE, a
+// LancirOut). The float RGBA copy of the source (`packed`) and the float
+// result (`lres`) are only allocated when an attempt uses them -- 16 bytes per
+// source and per destination pixel, per plan, spare and replica, that also
+// count against the plan cache: the automatic path of uint8 / uint16 images
+// touches neither. Every row whose condition holds, fastest first:
+//
+//   attempt        path   sides and condition                            launches
+//   k_lanc2h       0, 4   an owner's exact-2x RGBA call, half / bfloat16 k_lanc2h
+//                         pixels on a side the kernel may take: RAW 16-bit
+//                         / float RGBA | STORE 16-bit, or float of a unity
+//                         plan -- images that lanc2h_image_ok takes
+//   k_lanc2 raw    4      RAW uint8 / uint16 RGB(A) that lanc2_takes_raw k_lanc2
+//                         takes, `dst2`; STORE | FLOAT
+//   k_lanc2        4      FLOAT; STORE | FLOAT                           k_lanc2
+//   pass raw       5      RAW pixels that gpass_lancir_takes_raw takes   gpass_route's
+//                         (16-bit: `io16`); STORE | FLOAT
+//   pass           5, 4   FLOAT; STORE | FLOAT. On path 4: the automatic gpass_route's
+//                         path alone, when gpass_ok
+//   generic        any    FLOAT + FLOAT: the automatic path (and every   launch_lancir_generic
+//                         path but 4 and 5)
+//
+// STORE: an owner's call with `fio` and `out_fast`. A forced path 4 or 5 has
+// no generic attempt (`forced`). Every LANCIR road is `lazy`.
+static Road lanc_road( const RoadCall& C )
+{
+	const avirhip_plan* const p = C.p;
+	const avirhip_plan* const q = C.k;
+	const bool owner = ( q != p );
+	const ImageRef& img = C.img;
+	const void* const dst = C.dst;
+	const int qpath = C.path;
+	Road R;
+
+	R.n = 0;
+	R.lazy = true;
+	R.forced = ( q -> path != 0 && ( qpath == 4 || qpath == 5 ));
+
+	auto add = [&R]( const RoadFamily f, const bool raw, const bool store )
 	{
-		return( AVIRHIP_OK );
-	}
+		R.a[ R.n++ ] = RoadAttempt{ f, ( raw ? AVS_RAW : AVS_FLOAT ),
+			( store ? AVS_STORE : AVS_FLOAT ), AV1_NOTHING };
+	};
 
 	// (double and uint32 elements, lancir.h:373-377: the pack pass and the
 	// output stage convert them; the fast kernels' own loaders and fused stores
@@ -965,14 +969,10 @@ static int lancir_owner( avirhip_plan* p, const void* src, void* dst,
 	// kernels: both stages for every 16-bit image.
 	const bool h_in = dtype_is_float16_kind( p -> in_type );
 	const bool h_out = dtype_is_float16_kind( p -> out_type );
-	const int qpath = ( q -> path != 0 ? q -> path : q -> auto_path );
 	const bool io16 = ( qpath == 5 && q -> lanc2 == nullptr && gpass_io16() );
 	const bool in_fast = ( p -> in_type <= AVIRHIP_F32 || ( h_in && io16 ));
 	const bool out_fast = ( p -> out_type <= AVIRHIP_F32 || ( h_out && io16 &&
 		( (uintptr_t) dst & 1 ) == 0 ));
-	const ImageRef img = { src, p -> in_type, p -> io_ch, p -> src_stride };
-	const LancirOut ostage = { dst, p -> new_stride, p -> out_type, p -> io_ch,
-		p -> l_unity, p -> l_out_mul, p -> l_clamp };
 
 	// k_lanc2's integer stage behind a raw RGBA source stores a lane's two
 	// elements at once
@@ -984,39 +984,9 @@ static int lancir_owner( avirhip_plan* p, const void* src, void* dst,
 		( p -> out_type != AVIRHIP_F32 || ( (uintptr_t) dst & 3 ) == 0 ));
 
 	// (AVIRHIP_VARIANT_UP2_UNFUSED_IO: the process-wide switch, per plan)
-	const bool fio = ( fused_io() &&
+	const bool fio = ( owner && fused_io() &&
 		!( p -> variant & AVIRHIP_VARIANT_UP2_UNFUSED_IO ));
-
-	// the inner plan's first pass reads this image itself where it can;
-	// otherwise the pack pass makes its float RGBA copy
-	const ImageRef* raw = ( fio && in_fast &&
-		( gpass_lancir_takes_raw( q, img ) ||
-		( !h_in && lanc2_takes_raw( q, img ) && dst2 )) ? &img : nullptr );
-	const LancirOut* const lout = ( fio && out_fast ? &ostage : nullptr );
-
-	auto pack = [&]() -> int
-	{
-		// the source rows this band's vertical windows read
-		int sa, sb;
-		band_src_rows( p, row0, row1, &sa, &sb );
-
-		const int r = need_floats( p, &p -> packed,
-			(size_t) p -> src_w * p -> src_h * 4 );
-
-		if( r != 0 ) return( r );
-		verbose_stage( "pack pass", sb - sa + 1 );
-
-		return( launch_pack( (const char*) src + (size_t) sa *
-			p -> src_stride * dtype_size( p -> in_type ), p -> in_type,
-			p -> packed + (size_t) sa * p -> src_w * 4, p -> src_w,
-			sb - sa + 1, p -> io_ch, 4, p -> src_stride, st ));
-	};
-
-	auto need_lres = [&]() -> int
-	{
-		return( need_floats( p, &p -> lres,
-			(size_t) p -> new_w * p -> new_h * 4 ));
-	};
+	const bool store = ( fio && out_fast );
 
 	// Exact 2x RGBA with a half / bfloat16 image on either side (lanc2h.hip):
 	// one launch, on the automatic path whatever the frame's size (at exact 2x
@@ -1036,124 +1006,154 @@ static int lancir_owner( avirhip_plan* p, const void* src, void* dst,
 		( p -> path == 0 || p -> path == 4 ))
 	{
 		const bool src_own = (( h_in || p -> in_type == AVIRHIP_F32 ) &&
-			lanc2h_image_ok( src, p -> in_type, p -> src_stride ));
+			lanc2h_image_ok( img.ptr, p -> in_type, p -> src_stride ));
 		const bool dst_own = (( h_out || p -> l_unity ) &&
 			lanc2h_image_ok( dst, p -> out_type, p -> new_stride ));
 
 		if(( src_own && h_in ) || ( dst_own && h_out ))
 		{
-			if( !src_own && ( rc = pack()) != 0 ) return( rc );
-			if( !dst_own && ( rc = need_lres()) != 0 ) return( rc );
-
-			const ImageRef hsrc = ( src_own ? img : ImageRef{ p -> packed,
-				AVIRHIP_F32, 4, (long) p -> src_w * 4 });
-			const LancirOut hout = ( dst_own ? ostage : LancirOut{ p -> lres,
-				(long) p -> new_w * 4, AVIRHIP_F32, 4, 1, 1.0f, 0.0f });
-
-			rc = lanc2h_run( q, hsrc, hout, row0, row1, st );
-
-			if( rc == 0 && !dst_own )
-			{
-				verbose_stage( "output stage", row1 - row0 );
-				rc = launch_lancir_out( p, p -> lres, (long) p -> new_w * 4, dst,
-					row1 - row0, st );
-			}
-
-			if( rc != 1 )
-			{
-				return( rc );
-			}
+			add( AVF_LANC2H, src_own, dst_own );
 		}
 	}
 
-	if( raw == nullptr && ( rc = pack()) != 0 ) return( rc );
-
-	// (a null result buffer: only the fused store may run; a pass that would
-	// write the float result returns AVIRHIP_NEED_DST first)
-	if( lout == nullptr && ( rc = need_lres()) != 0 ) return( rc );
-
-	bool stored = false;
-
-	// (at most one round of each request: the kernel that was to read the
-	// owner's image refused the call -> float copy; a pass would have written
-	// the float result -> result buffer)
-	for( int round = 0; ; round++ )
+	// the inner plan's first pass reads the owner's image itself where it can;
+	// otherwise the pack pass makes its float RGBA copy
+	if( qpath == 4 )
 	{
-		rc = lancir_kernels( q, p -> packed, p -> lres, row0, row1, st,
-			SrcWindow{ 0, 0 }, raw, lout, stored );
-
-		if( rc != AVIRHIP_NEED_SRC && rc != AVIRHIP_NEED_DST )
+		if( fio && in_fast && !h_in && lanc2_takes_raw( q, img ) && dst2 )
 		{
-			break;
+			add( AVF_LANC2, true, store );
 		}
 
-		if( round == 2 )
-		{
-			set_error( "LANCIR: the inner plan kept asking for buffers (%d)", rc );
-			return( AVIRHIP_EINTERNAL );
-		}
-
-		if( rc == AVIRHIP_NEED_SRC )
-		{
-			raw = nullptr;
-			rc = pack();
-		}
-		else
-		{
-			rc = need_lres();
-		}
-
-		if( rc != 0 ) return( rc );
+		add( AVF_LANC2, false, store );
 	}
 
-	if( rc != 0 || stored )
+	if( qpath == 5 || ( qpath == 4 && q -> path == 0 && gpass_ok( q )))
 	{
-		return( rc );
+		// general-ratio pass kernels (vertical pass first)
+		// (a raw source on path 5 alone: gpass_lancir_takes_raw asks for it)
+		if( fio && in_fast && gpass_lancir_takes_raw( q, img ))
+		{
+			add( AVF_LPASS, true, store );
+		}
+
+		add( AVF_LPASS, false, store );
 	}
 
-	verbose_stage( "output stage", row1 - row0 );
-
-	if( p -> io_ch == 4 )
+	if( !R.forced )
 	{
-		return( launch_lancir_out( p, p -> lres, (long) p -> new_w * 4, dst,
-			row1 - row0, st ));
+		add( AVF_LGENERIC, false, false );
 	}
 
-	return( launch_lancir_out_pad( p, p -> lres, dst, row1 - row0, st ));
+	return( R );
+}
+
+// LANCIR's launchers by family, as avir_run_*. STORE: the owner's output stage
+static LancirOut lanc_ostage( const RoadCall& C )
+{
+	const avirhip_plan* const p = C.p;
+
+	return( LancirOut{ C.dst, p -> new_stride, p -> out_type, p -> io_ch,
+		p -> l_unity, p -> l_out_mul, p -> l_clamp });
+}
+
+static int lanc_run_lanc2h( RoadCall& C, const RoadAttempt& A )
+{
+	const ImageRef hsrc = ( A.src == AVS_RAW ? C.img : ImageRef{ C.fsrc,
+		AVIRHIP_F32, 4, C.fstride });
+	const LancirOut hout = ( A.res == AVS_STORE ? lanc_ostage( C ) :
+		LancirOut{ C.fdst, (long) C.p -> new_w * 4, AVIRHIP_F32, 4, 1, 1.0f,
+		0.0f });
+
+	return( lanc2h_run( C.k, hsrc, hout, C.row0, C.row1, C.st ));
+}
+
+static int lanc_run_lanc2( RoadCall& C, const RoadAttempt& A )
+{
+	const LancirOut ostage = lanc_ostage( C );
+
+	return( lanc2_run( C.k, C.fsrc, C.fdst, C.row0, C.row1, C.st, C.win,
+		( A.src == AVS_RAW ? &C.img : nullptr ),
+		( A.res == AVS_STORE ? &ostage : nullptr )));
+}
+
+static int lanc_run_pass( RoadCall& C, const RoadAttempt& A )
+{
+	const LancirOut ostage = lanc_ostage( C );
+
+	return( gpass_run( C.k, C.fsrc, C.fstride, C.fdst, C.row0, C.row1, C.st,
+		( A.src == AVS_RAW ? &C.img : nullptr ), nullptr,
+		( A.res == AVS_STORE ? &ostage : nullptr )));
+}
+
+static int lanc_run_generic( RoadCall& C, const RoadAttempt& )
+{
+	// (the generic kernels' intermediate is only allocated when they run)
+	const int rc = ensure_scratch( C.k );
+
+	return( rc != 0 ? rc : launch_lancir_generic( C.k, C.fsrc, C.fdst,
+		C.k -> resbuf, C.row0, C.row1, C.st ));
+}
+
+// The pack pass, at most once per call: the float copy of the caller's source
+// in `k`'s channel count (a LANCIR owner's: float RGBA)
+static int road_pack( RoadCall& C )
+{
+	avirhip_plan* const p = C.p;
+	const int ch = C.k -> ch;
+
+	if( !C.need_pack || C.packed )
+	{
+		return( AVIRHIP_OK );
+	}
+
+	C.packed = true;
+
+	// (a lazy call comes here without ensure_scratch; a no-op elsewhere)
+	const int ra = need_floats( p, &p -> packed, (size_t) p -> src_w *
+		p -> src_h * ch );
+
+	if( ra != 0 ) return( ra );
+	C.fsrc = p -> packed;
+
+	// a band converts the source rows its windows read, nothing else (the
+	// pipelined host-pointer call is 16 bands: 16 whole-frame packs otherwise)
+	int pa, pb;
+	band_src_rows( p, C.row0, C.row1, &pa, &pb );
+
+	if( pb < pa )
+	{
+		return( AVIRHIP_OK );
+	}
+
+	const char* const ps = (const char*) C.img.ptr + (size_t) pa *
+		p -> src_stride * dtype_size( p -> in_type );
+	float* const pd = p -> packed + (size_t) pa * p -> src_w * ch;
+	verbose_stage( "pack pass", pb - pa + 1 );
+
+	if( p -> gamma )
+	{
+		return( launch_pack_gamma( ps, p -> in_type, pd, p -> src_w,
+			pb - pa + 1, p -> io_ch, ch, p -> src_stride,
+			p -> alpha_index, p -> d_srgb_tbl, C.st ));
+	}
+
+	return( launch_pack( ps, p -> in_type, pd, p -> src_w, pb - pa + 1,
+		p -> io_ch, ch, p -> src_stride, C.st ));
 }
 
 // ---- AVIR ----
 
-// What belongs to one AVIR call. Two things change while it runs, here and
-// nowhere else. The float image the kernels read: the caller's own (float
-// pixels of the plan's channel count, no gamma), or the plan's `packed` copy,
-// which the pack pass fills at most once per call and only when a kernel is
-// about to read it (avir_pack). The float result: the caller's image when
-// `direct`, else the plan's `resbuf` -- null until something asked for it.
-struct AvirCall
-{
-	avirhip_plan* p;
-	int path;
-	ImageRef img;       // the caller's source
-	void* dst;          // the caller's result
-	int row0, row1;
-	hipStream_t st;
-	SrcWindow win;
-	bool need_pack;     // avir_need_pack
-	bool direct;        // avir_direct: the caller's image IS the float result
-	const float* fsrc;  // the float source, its pitch, ...
-	long fstride;
-	bool packed;        // ... and whether the pack pass has run for this call
-	float* fdst;
-};
-
+// What avir_road asks about a call, beside the plan: the classes of element
+// types, whether this call's pixels go through fused loads and stores at all,
+// and which results a path's last pass may store itself.
 static bool dtype_is_int( const int t )
 {
 	return( t == AVIRHIP_U8 || t == AVIRHIP_U16 );
 }
 
 // (AVIRHIP_VARIANT_UP2_UNFUSED_IO: the process-wide switch, per plan)
-static bool avir_fio( const AvirCall& C )
+static bool avir_fio( const RoadCall& C )
 {
 	return( fused_io() && !( C.path == 4 &&
 		( C.p -> variant & AVIRHIP_VARIANT_UP2_UNFUSED_IO )));
@@ -1165,7 +1165,7 @@ static bool avir_fio( const AvirCall& C )
 // (half / bfloat16 pixels: the marching kernel (4) and the last pass of
 // the pass kernels (5, 1-4 channels: gp_store_int_row) narrow and store
 // them; behind the tiles the output stage does)
-static bool avir_stores( const AvirCall& C )
+static bool avir_stores( const RoadCall& C )
 {
 	const avirhip_plan* const p = C.p;
 
@@ -1178,7 +1178,7 @@ static bool avir_stores( const AvirCall& C )
 
 // this result is the whole-ratio vertical kernel's to store (the two-pass
 // tiles, and k_dnfh's integer results): RGBA uint8 pixels are stored whole
-static bool avir_dn_stores( const AvirCall& C )
+static bool avir_dn_stores( const RoadCall& C )
 {
 	return( avir_stores( C ) && !( C.p -> out_type == AVIRHIP_U8 &&
 		C.p -> io_ch == 4 && ( (uintptr_t) C.dst & 3 ) != 0 ) &&
@@ -1238,26 +1238,7 @@ static long dnsrgb_store_maxpix()
 // make their sides ready: behind the sRGB kinds the float copies their road
 // expects to find (ensure_scratch), behind the 16-bit kinds `resbuf` -- also
 // where the tiles then store.
-enum AvirFamily { AVF_DNSRGB, AVF_DN16, AVF_TILES, AVF_UP2, AVF_GPASS,
-	AVF_GENERIC };
-enum AvirSide { AVS_FLOAT, AVS_RAW, AVS_STORE };
-enum AvirFirst { AV1_NOTHING, AV1_SCRATCH, AV1_RESBUF };
-
-struct AvirAttempt
-{
-	AvirFamily family;
-	AvirSide src, res;  // AVS_RAW | AVS_FLOAT, AVS_STORE | AVS_FLOAT
-	AvirFirst first;
-};
-
-struct AvirRoad
-{
-	int n;
-	AvirAttempt a[ 4 ];
-	bool lazy, forced;
-};
-
-static AvirRoad avir_road( const AvirCall& C )
+static Road avir_road( const RoadCall& C )
 {
 	const avirhip_plan* const p = C.p;
 	const int path = C.path;
@@ -1266,16 +1247,16 @@ static AvirRoad avir_road( const AvirCall& C )
 	const bool h_out = dtype_is_float16_kind( p -> out_type );
 	const bool dn_fio = ( path == 2 && p -> ch == 4 && fused_io() &&
 		!( p -> variant & AVIRHIP_VARIANT_DN_UNFUSED_IO ));
-	AvirFirst tiles_first = AV1_NOTHING;
-	AvirRoad R;
+	RoadFirst tiles_first = AV1_NOTHING;
+	Road R;
 
 	R.n = 0;
 	R.forced = ( p -> path != 0 && path >= 2 && path <= 5 );
 
-	auto add = [&R]( const AvirFamily f, const bool raw, const bool store,
-		const AvirFirst first )
+	auto add = [&R]( const RoadFamily f, const bool raw, const bool store,
+		const RoadFirst first )
 	{
-		R.a[ R.n++ ] = AvirAttempt{ f, ( raw ? AVS_RAW : AVS_FLOAT ),
+		R.a[ R.n++ ] = RoadAttempt{ f, ( raw ? AVS_RAW : AVS_FLOAT ),
 			( store ? AVS_STORE : AVS_FLOAT ), first };
 	};
 
@@ -1414,61 +1395,23 @@ static AvirRoad avir_road( const AvirCall& C )
 	return( R );
 }
 
-// The pack pass, at most once per call
-static int avir_pack( AvirCall& C )
+// the float result buffer of a call that is not `direct`: `resbuf`, a LANCIR
+// owner's `lres` ...
+static float*& road_res( const RoadCall& C )
 {
-	avirhip_plan* const p = C.p;
-
-	if( !C.need_pack || C.packed )
-	{
-		return( AVIRHIP_OK );
-	}
-
-	C.packed = true;
-
-	// (a lazy call comes here without ensure_scratch; a no-op elsewhere)
-	const int ra = need_floats( p, &p -> packed, (size_t) p -> src_w *
-		p -> src_h * p -> ch );
-
-	if( ra != 0 ) return( ra );
-	C.fsrc = p -> packed;
-
-	// a band converts the source rows its windows read, nothing else (the
-	// pipelined host-pointer call is 16 bands: 16 whole-frame packs otherwise)
-	int pa, pb;
-	band_src_rows( p, C.row0, C.row1, &pa, &pb );
-
-	if( pb < pa )
-	{
-		return( AVIRHIP_OK );
-	}
-
-	const char* const ps = (const char*) C.img.ptr + (size_t) pa *
-		p -> src_stride * dtype_size( p -> in_type );
-	float* const pd = p -> packed + (size_t) pa * p -> src_w * p -> ch;
-	verbose_stage( "pack pass", pb - pa + 1 );
-
-	if( p -> gamma )
-	{
-		return( launch_pack_gamma( ps, p -> in_type, pd, p -> src_w,
-			pb - pa + 1, p -> io_ch, p -> ch, p -> src_stride,
-			p -> alpha_index, p -> d_srgb_tbl, C.st ));
-	}
-
-	return( launch_pack( ps, p -> in_type, pd, p -> src_w, pb - pa + 1,
-		p -> io_ch, p -> ch, p -> src_stride, C.st ));
+	return( C.p -> is_lancir ? C.p -> lres : C.p -> resbuf );
 }
 
-// the float result buffer of a call that is not `direct`, when it is needed
-static int avir_need_res( const AvirCall& C )
+// ... when it is needed
+static int road_need_res( const RoadCall& C )
 {
-	return( C.direct ? AVIRHIP_OK : need_floats( C.p, &C.p -> resbuf,
-		(size_t) C.p -> new_w * C.p -> new_h * C.p -> ch ));
+	return( C.direct ? AVIRHIP_OK : need_floats( C.p, &road_res( C ),
+		(size_t) C.p -> new_w * C.p -> new_h * C.k -> ch ));
 }
 
 // ---- one function per family: its launcher, with the sides of the attempt.
 // Each returns the launcher's code -- 1: it cannot take this call.
-static int avir_run_dnfh( AvirCall& C, const AvirAttempt& A )
+static int avir_run_dnfh( RoadCall& C, const RoadAttempt& A )
 {
 	const ImageRef hsrc = ( A.src == AVS_RAW ? C.img : ImageRef{ C.fsrc,
 		AVIRHIP_F32, 4, C.fstride });
@@ -1479,7 +1422,7 @@ static int avir_run_dnfh( AvirCall& C, const AvirAttempt& A )
 		fused_run_dn16( C.p, hsrc, C.fdst, C.row0, C.row1, C.st, hout ));
 }
 
-static int avir_run_tiles( AvirCall& C, const AvirAttempt& A )
+static int avir_run_tiles( RoadCall& C, const RoadAttempt& A )
 {
 	avirhip_plan* const p = C.p;
 	void* const iout = ( A.res == AVS_STORE ? C.dst : nullptr );
@@ -1491,7 +1434,7 @@ static int avir_run_tiles( AvirCall& C, const AvirAttempt& A )
 		C.row0, C.row1, C.st, iout ));
 }
 
-static int avir_run_up2( AvirCall& C, const AvirAttempt& A )
+static int avir_run_up2( RoadCall& C, const RoadAttempt& A )
 {
 	if( A.res == AVS_STORE )
 	{
@@ -1506,7 +1449,7 @@ static int avir_run_up2( AvirCall& C, const AvirAttempt& A )
 		C.win, nullptr, nullptr ));
 }
 
-static int avir_run_gpass( AvirCall& C, const AvirAttempt& A )
+static int avir_run_gpass( RoadCall& C, const RoadAttempt& A )
 {
 	void* const iout = ( A.res == AVS_STORE ? C.dst : nullptr );
 
@@ -1517,18 +1460,31 @@ static int avir_run_gpass( AvirCall& C, const AvirAttempt& A )
 		nullptr, iout, nullptr ));
 }
 
-static int avir_run_generic( AvirCall& C, const AvirAttempt& )
+static int avir_run_generic( RoadCall& C, const RoadAttempt& )
 {
 	return( run_generic( C.p, C.fsrc, C.fstride, C.fdst, C.row0, C.row1,
 		C.st ));
 }
 
-// The tail of an AVIR call whose float result is at `fdst` (and is not the
-// caller's image): error diffusion or the output stage into `dst`.
-static int avir_output( avirhip_plan* p, const float* fdst, void* dst,
-	int row0, int row1, hipStream_t st )
+// The tail of a call whose float result is at `fdst` (and is not the caller's
+// image): the owner's output stage (LANCIR), error diffusion or the output
+// stage (AVIR) into `dst`.
+static int road_output( const RoadCall& C )
 {
+	avirhip_plan* const p = C.p;
+	const float* const fdst = C.fdst;
+	void* const dst = C.dst;
+	const int row0 = C.row0, row1 = C.row1;
+	const hipStream_t st = C.st;
+
 	verbose_stage( "output stage", row1 - row0 );
+
+	if( p -> is_lancir )
+	{
+		return( p -> io_ch == 4 ?
+			launch_lancir_out( p, fdst, (long) p -> new_w * 4, dst, row1 - row0,
+			st ) : launch_lancir_out_pad( p, fdst, dst, row1 - row0, st ));
+	}
 
 	if( p -> dither == AVIRHIP_DITHER_ERRD )
 	{
@@ -1563,29 +1519,31 @@ static int avir_output( avirhip_plan* p, const float* fdst, void* dst,
 // The attempts of a road in turn, each with its sides made ready, until one
 // does not refuse the call; then the output stage, unless the last pass stored
 // the caller's pixels or the caller's image is the float result.
-static int avir_execute( AvirCall& C, const AvirRoad& R )
+static int road_execute( RoadCall& C, const Road& R )
 {
-	static int ( * const run[] )( AvirCall&, const AvirAttempt& ) = {
+	static int ( * const run[] )( RoadCall&, const RoadAttempt& ) = {
 		avir_run_dnfh, avir_run_dnfh, avir_run_tiles, avir_run_up2,
-		avir_run_gpass, avir_run_generic }; // (by AvirFamily)
+		avir_run_gpass, avir_run_generic, lanc_run_lanc2h, lanc_run_lanc2,
+		lanc_run_pass, lanc_run_generic }; // (by RoadFamily)
 	avirhip_plan* const p = C.p;
 	bool stored = false;
 	int rc = 1;
 
 	for( int i = 0; i < R.n && rc == 1; i++ )
 	{
-		const AvirAttempt& A = R.a[ i ];
+		const RoadAttempt& A = R.a[ i ];
 
 		if( A.first == AV1_SCRATCH && ( rc = ensure_scratch( p )) != 0 )
 			return( rc );
 
-		if( A.first == AV1_RESBUF && ( rc = avir_need_res( C )) != 0 )
+		if( A.first == AV1_RESBUF && ( rc = road_need_res( C )) != 0 )
 			return( rc );
 
-		if( A.src == AVS_FLOAT && ( rc = avir_pack( C )) != 0 ) return( rc );
-		if( A.res == AVS_FLOAT && ( rc = avir_need_res( C )) != 0 ) return( rc );
+		// (the pack before the result buffer of the same attempt)
+		if( A.src == AVS_FLOAT && ( rc = road_pack( C )) != 0 ) return( rc );
+		if( A.res == AVS_FLOAT && ( rc = road_need_res( C )) != 0 ) return( rc );
 
-		C.fdst = ( C.direct ? (float*) C.dst : p -> resbuf );
+		C.fdst = ( C.direct ? (float*) C.dst : road_res( C ));
 		rc = run[ A.family ]( C, A );
 		stored = ( rc == 0 && A.res == AVS_STORE );
 	}
@@ -1602,14 +1560,15 @@ static int avir_execute( AvirCall& C, const AvirRoad& R )
 		return( rc ); // (no epilogue)
 	}
 
-	return( avir_output( p, C.fdst, C.dst, C.row0, C.row1, C.st ));
+	return( road_output( C ));
 }
 
 static int exec_avir( avirhip_plan* p, const void* src, void* dst, int row0,
 	int row1, hipStream_t st, const SrcWindow win )
 {
-	AvirCall C;
+	RoadCall C;
 	C.p = p;
+	C.k = p;
 	C.path = ( p -> path != 0 ? p -> path : p -> auto_path );
 	C.img = ImageRef{ src, p -> in_type, p -> io_ch, p -> src_stride };
 	C.dst = dst;
@@ -1624,13 +1583,47 @@ static int exec_avir( avirhip_plan* p, const void* src, void* dst, int row0,
 	C.packed = false;
 	C.fdst = nullptr;
 
-	const AvirRoad R = avir_road( C );
+	const Road R = avir_road( C );
 
-	// (a lazy road makes neither float copy: avir_pack and avir_need_res
+	// (a lazy road makes neither float copy: road_pack and road_need_res
 	// allocate them where an attempt needs them after all)
 	const int rc = ( R.lazy ? AVIRHIP_OK : ensure_scratch( p ));
 
-	return( rc != 0 ? rc : avir_execute( C, R ));
+	return( rc != 0 ? rc : road_execute( C, R ));
+}
+
+// A LANCIR call. The owner: a plan with an inner plan, unless it is forced to
+// path 1 (its own generic kernels, whatever its pixels). `win` is a plain
+// plan's alone, and k_lanc2's.
+static int exec_lancir( avirhip_plan* p, const void* src, void* dst, int row0,
+	int row1, hipStream_t st, const SrcWindow win )
+{
+	const bool owner = ( p -> inner != nullptr && p -> path != 1 );
+
+	if( owner && row1 <= row0 )
+	{
+		return( AVIRHIP_OK );
+	}
+
+	RoadCall C;
+	C.p = p;
+	C.k = ( owner ? p -> inner : p );
+	C.path = ( C.k -> path != 0 ? C.k -> path : C.k -> auto_path );
+	C.img = ImageRef{ src, p -> in_type, p -> io_ch, p -> src_stride };
+	C.dst = dst;
+	C.row0 = row0; C.row1 = row1;
+	C.st = st;
+	C.win = ( owner ? SrcWindow{ 0, 0 } : win );
+	C.need_pack = owner;
+	C.direct = !owner;
+	// (a raw source's kernels are handed the float copy of an earlier call, or
+	// none: they do not read it)
+	C.fsrc = ( owner ? p -> packed : (const float*) src );
+	C.fstride = C.k -> src_stride;
+	C.packed = false;
+	C.fdst = nullptr;
+
+	return( road_execute( C, lanc_road( C )));
 }
 
 // One call on device-resident buffers, by route.
@@ -1644,19 +1637,8 @@ static int exec_device( avirhip_plan* p, const void* src, void* dst,
 		return( exec_f64( p, src, dst, row0, row1, st ));
 	}
 
-	if( !p -> is_lancir )
-	{
-		return( exec_avir( p, src, dst, row0, row1, st, win ));
-	}
-
-	if( p -> inner != nullptr && p -> path != 1 )
-	{
-		return( lancir_owner( p, src, dst, row0, row1, st ));
-	}
-
-	bool stored;
-	return( lancir_kernels( p, (const float*) src, (float*) dst, row0, row1,
-		st, win, nullptr, nullptr, stored ));
+	return( p -> is_lancir ? exec_lancir( p, src, dst, row0, row1, st, win ) :
+		exec_avir( p, src, dst, row0, row1, st, win ));
 }
 
 } // namespace avirhip

@@ -1438,7 +1438,7 @@ int gpass_last_src_row( const avirhip_plan* p, int row0, int row1 )
 // types the loaders know -- uint8, uint16, float, half, bfloat16; k_lf's own
 // test, lfuse_takes_raw, asks the same of base and pitch). The owner offers a
 // half / bfloat16 image only on this path and not under AVIRHIP_GP_NO_IO16
-// (lancir_owner).
+// (api.cpp, lanc_road).
 bool gpass_lancir_takes_raw( const avirhip_plan* p, const ImageRef& img )
 {
 	const GPData* D = (const GPData*) p -> gpass;
@@ -1635,10 +1635,9 @@ static GPLOut gp_make_lout( const avirhip_plan* p, const LancirOut& o )
 //
 //   outcome        plan     condition                                       launches
 //   refuse         LANCIR   an axis without its gather geometry             --
-//   need dst       LANCIR   no result buffer and no owner's output stage    --
 //   lanc fused     LANCIR   k_lf's strips exist, the fusion pays (lf_pays),   k_lf
 //                           k_lf reads `raw` if there is one, not UPG_TWO_PASS
-//   lanc two-pass  LANCIR   otherwise (a refused `raw`: AVIRHIP_NEED_SRC)     k_gv, k_gh
+//   lanc two-pass  LANCIR   otherwise (a refused `raw`: 1, as every refusal)  k_gv, k_gh
 //   avir fused     AVIR     12-tap upsizing on both axes from float RGBA,   k_gf
 //                           7 Mpixels of output or UPG_FUSED, not UPG_TWO_PASS
 //   refuse         AVIR     an axis on the gather kernels (sa_wanted says     --
@@ -1655,7 +1654,10 @@ static GPLOut gp_make_lout( const avirhip_plan* p, const LancirOut& o )
 //
 // An accumulation pass that refuses a call's pointers (sacc_run_axis: 1) falls
 // back to the gather kernels of its axis, an optimistic run to the two-pass one.
-enum GPOutcome { GPR_REFUSE, GPR_NEED_DST, GPR_LANC_FUSED, GPR_LANC_TWO_PASS,
+// Where a LANCIR call's float result goes is not this table's matter: without
+// an owner's output stage (`lout`) the last pass writes `dst`, which api.cpp's
+// road (lanc_road) made ready before the attempt: `lres`, or the caller's rows.
+enum GPOutcome { GPR_REFUSE, GPR_LANC_FUSED, GPR_LANC_TWO_PASS,
 	GPR_AVIR_FUSED, GPR_AVIR_OPTIMISTIC, GPR_AVIR_TWO_PASS };
 enum GPFamily { GPF_GATHER, GPF_ACC };
 enum GPAccForm { GPA_EXACT, GPA_FINITE, GPA_LADDER };
@@ -1675,8 +1677,7 @@ static const GPRoute gp_refuse = { GPR_REFUSE, GPF_GATHER, GPF_GATHER,
 	GPA_EXACT, false, false };
 
 static GPRoute route_lancir( const avirhip_plan* p, const GPData* D,
-	const float* dst, const ImageRef* raw, const LancirOut* lout,
-	const double lf_ratio )
+	const ImageRef* raw, const LancirOut* lout, const double lf_ratio )
 {
 	GPRoute R = gp_refuse;
 	const bool two_pass = (( p -> variant & AVIRHIP_VARIANT_UPG_TWO_PASS ) != 0 );
@@ -1714,8 +1715,7 @@ static GPRoute route_lancir( const avirhip_plan* p, const GPData* D,
 		return( R );
 	}
 
-	R.outcome = ( dst == nullptr && lout == nullptr ? GPR_NEED_DST :
-		use_lf ? GPR_LANC_FUSED : GPR_LANC_TWO_PASS );
+	R.outcome = ( use_lf ? GPR_LANC_FUSED : GPR_LANC_TWO_PASS );
 	R.need_mid = ( R.outcome == GPR_LANC_TWO_PASS );
 	return( R );
 }
@@ -1813,13 +1813,12 @@ static GPRoute route_avir( const avirhip_plan* p, const GPData* D,
 
 // (the tuning aid is read by the first call of any plan, as gf_minpix's is)
 static GPRoute gpass_route( const avirhip_plan* p, const GPData* D,
-	const float* dst, const ImageRef* raw, const bool has_out,
-	const LancirOut* lout )
+	const ImageRef* raw, const bool has_out, const LancirOut* lout )
 {
 	static const double lf_ratio = ( getenv( "AVIRHIP_LF_INT_RATIO" ) != nullptr ?
 		atof( getenv( "AVIRHIP_LF_INT_RATIO" )) : -1.0 );
 
-	return( p -> is_lancir ? route_lancir( p, D, dst, raw, lout, lf_ratio ) :
+	return( p -> is_lancir ? route_lancir( p, D, raw, lout, lf_ratio ) :
 		route_avir( p, D, raw, has_out ));
 }
 
@@ -1899,9 +1898,10 @@ static int run_lanc_two_pass( const avirhip_plan* p, const GPData* D,
 
 	if( rc != 0 )
 	{
-		// (the kernel refuses the image after all: the owner makes the float
-		// copy and calls again)
-		return( rc == 1 && C.raw != nullptr ? AVIRHIP_NEED_SRC : rc );
+		// (1: the kernel refuses the image after all, as any refusal -- the
+		// road's next attempt reads the pack pass's float copy; `mid` stays
+		// allocated for it)
+		return( rc );
 	}
 
 	GPPass H;
@@ -2179,7 +2179,7 @@ int gpass_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 		return( AVIRHIP_OK );
 	}
 
-	const GPRoute R = gpass_route( p, D, dst, raw, iout != nullptr, lout );
+	const GPRoute R = gpass_route( p, D, raw, iout != nullptr, lout );
 	int rc;
 
 	if( R.need_mid && ( rc = gp_lazy_alloc( p, D, D -> mid, D -> mid_bytes,
@@ -2198,7 +2198,6 @@ int gpass_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 
 	switch( R.outcome )
 	{
-		case GPR_NEED_DST: return( AVIRHIP_NEED_DST );
 		case GPR_LANC_FUSED: return( run_lanc_fused( p, D, C ));
 		case GPR_LANC_TWO_PASS: return( run_lanc_two_pass( p, D, C ));
 		case GPR_AVIR_FUSED: return( run_avir_fused( p, D, C ));

@@ -473,7 +473,7 @@ __device__ __forceinline__ void gp_store_lancir( const GPLOut& O,
 // bfloat16: v_cvt_pk_bf16_f32, the header's integer formula, NaN stays NaN.
 // RGBA: one 8-byte store per lane (any 2-byte-aligned address: 512 contiguous
 // bytes per wave row); 1-3 channels: element stores. The host offers this store
-// only for an even base address (lancir_owner).
+// only for an even base address (api.cpp, lanc_road).
 __device__ __forceinline__ void gp_store_lancir_f16( const GPLOut& O,
 	const long row, const int x, const f4 o, const bool ok )
 {

@@ -199,7 +199,7 @@ int gpass_run_v( const GPAxis& A_, int v_blk, int v_rs, int v_rc,
 	}
 #endif
 	// (1: no kernel of the variant group takes this plan -- the caller falls
-	// back, api.cpp turns an unexpected 1 into AVIRHIP_NEED_SRC / the generic path)
+	// back: api.cpp's road goes on to its next attempt, behind the pack pass)
 	if( launch_gv( P, wp, items, lds, st ) != 0 )
 	{
 		return( 1 );

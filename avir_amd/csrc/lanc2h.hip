@@ -32,7 +32,7 @@
 // or destination distance limit exists and the host checks none.
 //
 // Alignment: a pixel is naturally aligned on both sides -- the ONE predicate of
-// the routing (api.cpp, lancir_owner) and of lanc2h_run's refusal:
+// the routing (api.cpp, lanc_road) and of lanc2h_run's refusal:
 //
 //   bool lanc2h_image_ok( const void* ptr, int type, long stride )
 //   {

@@ -48,13 +48,13 @@ __device__ __forceinline__ float avirhip_x86_round_fix( const float a,
 	return( fabsf( a ) >= 2147483648.0f ? ( a < 0.0f ? pk_out : 0.0f ) : t );
 }
 
-// internal: an inner plan was run without a float result buffer and its path
-// would have written one (exec_device allocates it and runs again)
-#define AVIRHIP_NEED_DST 1001
-// internal: an inner plan was handed its owner's image to read as it is (an
-// ImageRef) and the kernel that would have done so refused the call: the owner
-// runs the pack pass and calls again with the float copy
-#define AVIRHIP_NEED_SRC 1002
+// Return codes of the kernel families' launchers (the *_run functions below):
+// AVIRHIP_OK -- the call's rows are enqueued; an AVIRHIP_E* code -- it failed;
+// 1 -- the launcher cannot take THIS call (its pointers' alignment, a source
+// window, an element type): nothing was launched and nothing is wrong. There
+// is no other private code: api.cpp's road (avir_road, lanc_road) lists the
+// attempts of a call up front, makes the buffers of the next one ready and
+// goes on to it.
 
 namespace avirhip {
 
@@ -233,7 +233,7 @@ struct ImageRef
 // into the owner's image -- `dst` is the band's first row there -- and no float
 // result is written. lanc2_run and gpass_run that return 0 for a call with a
 // `lout` HAVE stored the owner's pixels: what they cannot store they refuse
-// (1, AVIRHIP_NEED_*).
+// (1).
 struct LancirOut
 {
 	void* dst;

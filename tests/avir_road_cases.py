@@ -23,7 +23,7 @@ from tests import refbind as rb
 from tests import dnf16_cases as D16
 from tests.gpass_route_cases import environment  # noqa: F401 (the test's)
 
-T = D16.T
+T = dict(D16.T, f64=(abi.F64, np.float64))   # (f64: tests/lanc_road_cases.py)
 GUARD = 0x5a
 MAX_SRC_PIXELS = 600 * 402
 P2, P3, P4, P5 = 2, 3, 4, abi.PATH_GPASS

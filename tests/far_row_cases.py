@@ -284,7 +284,7 @@ for _n, _f in (("u8c4", U8C4), ("u8c3", U8C3), ("u16c4", U16C4)):
          also=[("lanc2.hip:185", "( (unsigned) sy * (unsigned) P.raw_ss + "
                 "rcol );")])
 # ---- 8-byte elements: CLancIR's raw rows, and the double pipeline
-N_F64 = ("double rows are read by the pack pass alone (lancir_owner: in_fast "
+N_F64 = ("double rows are read by the pack pass alone (lanc_road: in_fast "
          "is false), one 64-bit address per pixel")
 Q_PACK = "const long e = (long) y * src_stride + (long) x * CH;"
 _row("lanc_f64_pack", ["generic.hip"], "lancir", LX2,

@@ -14,7 +14,7 @@ def _table():
     with open(os.path.join(ROOT, "avir_amd", "csrc", "api.cpp")) as fh:
         text = fh.read()
     head = text.index("//   attempt        path   condition")
-    body = text[head:text.index("static AvirRoad avir_road(", head)]
+    body = text[head:text.index("static Road avir_road(", head)]
     names = []
     for line in body.split("\n")[1:]:
         m = re.match(r"^//   (\S.*?)\s{2,}\S", line)

@@ -4,7 +4,10 @@ memory between guard bytes, against the reference. Raw words are compared, the
 bar is 0 differing words; the guard bytes stay untouched; and the stages and
 kernels the whole-frame call names under AVIRHIP_VERBOSE are the row's list, in
 order -- the road the call took, recorded from the library before avir_road
-(tools/avir_road_trace.py, profiles/avir_road/)."""
+(tools/avir_road_trace.py, profiles/avir_road/).
+
+check_road is the body of this test and of tests/test_gpu_lanc_roads.py's: `R`
+is the case module, `same` its comparison."""
 import re
 import pytest
 from avir_amd import abi
@@ -22,7 +25,7 @@ def _same(r, got, want, what):
     D16.same(got.view(want.dtype), want, r["tout"], what)
 
 
-def _frame(lib, r, p, sptr, capfd):
+def _frame(R, lib, r, p, sptr, capfd):
     with R.environment(dict(r["env"], AVIRHIP_VERBOSE="1")):
         capfd.readouterr()
         rcs, got, clean = R.run(lib, p, r, sptr, [(0, r["geom"][3])])
@@ -30,8 +33,7 @@ def _frame(lib, r, p, sptr, capfd):
     return rcs[0], got, clean, tags
 
 
-@pytest.mark.parametrize("name", R.NAMES)
-def test_road(name, capfd):
+def check_road(R, name, capfd, same):
     lib = abi.load()
     abi.check(lib.avirhip_init(0), "init")
     r = R.row(name)
@@ -39,7 +41,7 @@ def test_road(name, capfd):
     keep, sptr = R.device_source(r, src)
     with R.environment(r["env"]):
         obj, p = R.plan(r)
-    rc, got, clean, tags = _frame(lib, r, p, sptr, capfd)
+    rc, got, clean, tags = _frame(R, lib, r, p, sptr, capfd)
     print(name, rc, tags)
     assert clean, name + ": stored outside the image"
     if r["rc"] != 0:
@@ -50,10 +52,10 @@ def test_road(name, capfd):
             b"path %d cannot run this call (unaligned buffers?)" % r["path"])
         assert (got == R.GUARD).all(), "a refused call wrote its destination"
         obj, p = R.plan(r, 0)
-        rc, got, clean, tags = _frame(lib, r, p, sptr, capfd)
+        rc, got, clean, tags = _frame(R, lib, r, p, sptr, capfd)
         assert clean, name + ": stored outside the image (automatic path)"
     assert rc == 0, (rc, lib.avirhip_last_error())
-    _same(r, got, want, name + " frame")
+    same(r, got, want, name + " frame")
     assert tags == r["tags"], (name, tags)
     calls = R.bands(r)
     if calls:
@@ -61,4 +63,9 @@ def test_road(name, capfd):
             rcs, got, clean = R.run(lib, p, r, sptr, calls)
         assert rcs == [0] * len(calls), (rcs, lib.avirhip_last_error())
         assert clean, name + ": a band stored outside the image"
-        _same(r, got, want, name + " bands")
+        same(r, got, want, name + " bands")
+
+
+@pytest.mark.parametrize("name", R.NAMES)
+def test_road(name, capfd):
+    check_road(R, name, capfd, _same)

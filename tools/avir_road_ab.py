@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What AVIR's host dispatch costs on two builds of the library, in one
+"""What the host dispatch of a call costs on two builds of the library, in one
 process: PARENT.so, a copy of PARENT.so (the control: what loading the same
 code a second time is worth) and the tree's library are loaded side by side,
 each with its own plan on the same device images; timed loops of about 0.2 s
@@ -9,7 +9,8 @@ and the difference to PARENT's median, this library beside the control; and
 whether the three outputs are bit-identical.
 
 Workloads: bench.py's cfg2, cfg3 and cfg4; one k_dnfh uint8 -> uint8 sRGB call
-and one path-5 half -> half call, at the sizes of tools/half_timing.py.
+and one path-5 half -> half call, at the sizes of tools/half_timing.py; and
+CLancIR's: bench.py's cfg5 and lanc_up2_rgba8, one path-5 half -> half call.
 
   python tools/avir_road_ab.py PARENT.so PARENT_COPY.so [REPS=5]
 """
@@ -20,12 +21,16 @@ import sys
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
 
-# (name, sw, sh, nw, nh, type in, type out, ResBitDepth, gamma)
+# (name, sw, sh, nw, nh, type in, type out, ResBitDepth; 0: CLancIR, gamma)
 WORK = [("cfg2", 1920, 1080, 3840, 2160, "f32", "f32", 16, False),
         ("cfg3", 3840, 2160, 7680, 4320, "f32", "f32", 16, False),
         ("cfg4", 3840, 2160, 1280, 720, "f32", "f32", 16, False),
         ("k_dnfh sRGB u8->u8", 3840, 2160, 1280, 720, "u8", "u8", 8, True),
-        ("path 5 f16->f16", 1920, 1080, 2500, 1400, "f16", "f16", 16, False)]
+        ("path 5 f16->f16", 1920, 1080, 2500, 1400, "f16", "f16", 16, False),
+        ("cfg5", 3840, 2160, 7680, 4320, "f32", "f32", 0, False),
+        ("lanc_up2_rgba8", 1920, 1080, 3840, 2160, "u8", "u8", 0, False),
+        ("lancir path 5 f16->f16", 1920, 1080, 2500, 1400, "f16", "f16", 0,
+         False)]
 
 
 def main(argv):
@@ -53,8 +58,13 @@ def main(argv):
                 v = avir_amd.CImageResizerVars()
                 v.UseSRGBGamma, v.AlphaIndex = 1, 3
             with abi.using(L):
-                r = avir_amd.CImageResizer(bits)
-                p = r.plan(sw, sh, nw, nh, 4, 0.0, v, TT[tin][0], TT[tout][0])
+                if bits == 0:
+                    r = avir_amd.CLancIR()
+                    p = r.plan(sw, sh, nw, nh, 4, None, TT[tin][0], TT[tout][0])
+                else:
+                    r = avir_amd.CImageResizer(bits)
+                    p = r.plan(sw, sh, nw, nh, 4, 0.0, v, TT[tin][0],
+                               TT[tout][0])
             d = torch.zeros((nh, nw, 4), dtype=TT[tout][1], device=dev)
             keep.append((r, d))
             ms = C.c_double()

@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
-"""Runs every row of tests/avir_road_cases.py once on one build of the library
-and writes, per row and call (the whole frame, then each band): the tags of the
+"""Runs every row of tests/avir_road_cases.py (--cases lanc:
+tests/lanc_road_cases.py) once on one build of the library and writes, per row and call (the whole frame, then each band): the tags of the
 call's AVIRHIP_VERBOSE lines in order, its return code, the device bytes the
 plan holds after it (avirhip_plan_device_bytes) and a hash of the destination's
 bytes. No reference is computed. Two builds are compared by running this once
 per build -- each in a process of its own, the library named by AVIRHIP_LIB as
 tools/ab_libs.sh names it -- and taking a `diff` of the two files
-(profiles/avir_road/).
+(profiles/avir_road/, profiles/lanc_road/).
 
-  python tools/avir_road_trace.py --lib PATH --out FILE [--row NAME ...]
+  python tools/avir_road_trace.py [--cases avir|lanc] --lib PATH --out FILE
+                                  [--row NAME ...]
 """
 import argparse
 import hashlib
@@ -72,11 +73,13 @@ def main():
     ap.add_argument("--lib", help="the library to load instead of the tree's")
     ap.add_argument("--out", required=True)
     ap.add_argument("--row", action="append")
+    ap.add_argument("--cases", choices=("avir", "lanc"), default="avir")
     a = ap.parse_args()
     if a.lib:
         os.environ["AVIRHIP_LIB"] = os.path.abspath(a.lib)  # (read on import)
     from avir_amd import abi
-    from tests import avir_road_cases as R
+    import importlib
+    R = importlib.import_module("tests.%s_road_cases" % a.cases)
     lib = abi.load()
     abi.check(lib.avirhip_init(0), "init")
     with open(a.out, "w") as out:
