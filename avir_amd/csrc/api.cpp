@@ -192,8 +192,40 @@ static int need_floats( avirhip_plan* p, float** buf, size_t n )
 
 // ---- lowering of one AVIR axis (see plan.h for the view semantics) ----
 
-static int lower_axis( const avirhip_axis& ax, int src_len, int dst_len,
-	LAxis& L, const bool f64 = false )
+// a step's tables in the working type F: the float or the double fields of
+// the public structures (include/avirhip.h); `x` of an avirhip_rpos
+template< typename F >
+struct StepTab
+{
+	const F* flt; const F* suffix_dc; const F* prefix_dc; const F* phase_taps;
+	F avirhip_rpos::* x;
+};
+
+template< typename F >
+static StepTab< F > step_tab( const avirhip_step& s )
+{
+	if constexpr( sizeof( F ) == sizeof( double ))
+	{
+		return( StepTab< F >{ s.flt64, s.suffix_dc64, s.prefix_dc64,
+			s.phase_taps64, &avirhip_rpos::x64 });
+	}
+	else
+	{
+		return( StepTab< F >{ s.flt, s.suffix_dc, s.prefix_dc, s.phase_taps,
+			&avirhip_rpos::x });
+	}
+}
+
+template< typename T >
+static void null_tabs( const T& t )
+{
+	t.d_flt = nullptr; t.d_coef = nullptr; t.d_sdc = nullptr; t.d_pdc = nullptr;
+}
+
+// (F: float, or double for a double plan; the other type's tables stay empty)
+template< typename F >
+static int lower_axis_as( const avirhip_axis& ax, int src_len, int dst_len,
+	LAxis& L )
 {
 	L.ops.clear();
 	L.src_len = src_len;
@@ -214,6 +246,7 @@ static int lower_axis( const avirhip_axis& ax, int src_len, int dst_len,
 	for( int si = 0; si < ax.n_steps; si++ )
 	{
 		const avirhip_step& s = ax.steps[ si ];
+		const StepTab< F > st = step_tab< F >( s );
 
 		if( s.in_len != cur_len )
 		{
@@ -230,22 +263,21 @@ static int lower_axis( const avirhip_axis& ax, int src_len, int dst_len,
 		}
 
 		LOp op;
+		const auto ot = op_tab< F >( op );
 		op.type = 0; op.view = ( prev_upf ? VIEW_RAW : VIEW_CLAMP );
 		op.in_len = s.in_len; op.in_prefix = ( prev_upf ? prev_prefix : 0 );
 		op.zs_mmax = 0x7fffffff;
 		op.out_len = s.out_len; op.out_prefix = 0; op.out_total = s.out_len;
-		op.rf = 1; op.lat = 0; op.e = 0; op.d_flt = nullptr;
-		op.d_flt64 = nullptr; op.d_coef64 = nullptr; op.d_sdc64 = nullptr;
-		op.d_pdc64 = nullptr;
+		op.rf = 1; op.lat = 0; op.e = 0;
 		op.maxtaps = 0; op.d_start = nullptr; op.d_ntaps = nullptr;
-		op.d_coef = nullptr;
 		op.flen = 0; op.up_inprefix = 0; op.up_R = 0; op.sdc_len = 0;
-		op.pdc_len = 0; op.pdc_d0 = 0; op.d_sdc = nullptr; op.d_pdc = nullptr;
+		op.pdc_len = 0; op.pdc_d0 = 0;
+		null_tabs( op_tab< float >( op ));
+		null_tabs( op_tab< double >( op ));
 
 		if( s.kind == AVIRHIP_STEP_FIR )
 		{
-			if( s.resample_factor < 1 ||
-				( f64 ? (const void*) s.flt64 : (const void*) s.flt ) == nullptr ||
+			if( s.resample_factor < 1 || st.flt == nullptr ||
 				s.flt_latency < 0 || s.flt_len != 2 * s.flt_latency + 1 )
 			{
 				set_error( "step %d: malformed FIR (len %d, latency %d)", si,
@@ -258,14 +290,7 @@ static int lower_axis( const avirhip_axis& ax, int src_len, int dst_len,
 			op.lat = s.flt_latency;
 			op.e = s.edge_pixel_count;
 
-			if( f64 )
-			{
-				op.h_flt64.assign( s.flt64 + s.flt_latency, s.flt64 + s.flt_len );
-			}
-			else
-			{
-				op.h_flt.assign( s.flt + s.flt_latency, s.flt + s.flt_len );
-			}
+			ot.h_flt.assign( st.flt + s.flt_latency, st.flt + s.flt_len );
 
 			if( prev_upf )
 			{
@@ -303,8 +328,7 @@ static int lower_axis( const avirhip_axis& ax, int src_len, int dst_len,
 		else
 		if( s.kind == AVIRHIP_STEP_UP_FILTERED )
 		{
-			if( s.resample_factor < 2 ||
-				( f64 ? (const void*) s.flt64 : (const void*) s.flt ) == nullptr ||
+			if( s.resample_factor < 2 || st.flt == nullptr ||
 				s.flt_len < 1 || prev_upf )
 			{
 				set_error( "step %d: malformed filtered upsample", si );
@@ -316,14 +340,7 @@ static int lower_axis( const avirhip_axis& ax, int src_len, int dst_len,
 			op.rf = s.resample_factor;
 			op.flen = s.flt_len;
 
-			if( f64 )
-			{
-				op.h_flt64.assign( s.flt64, s.flt64 + s.flt_len );
-			}
-			else
-			{
-				op.h_flt.assign( s.flt, s.flt + s.flt_len );
-			}
+			ot.h_flt.assign( st.flt, st.flt + s.flt_len );
 
 			op.up_inprefix = s.in_prefix;
 			op.up_R = s.in_prefix + s.in_len + s.in_suffix;
@@ -343,24 +360,12 @@ static int lower_axis( const avirhip_axis& ax, int src_len, int dst_len,
 			}
 
 			// stash DC tails behind the filter taps: [flt | sdc | pdc]
-			if( f64 )
-			{
-				if( s.suffix_dc_len > 0 )
-					op.h_flt64.insert( op.h_flt64.end(), s.suffix_dc64,
-						s.suffix_dc64 + s.suffix_dc_len );
-				if( s.prefix_dc_len > 0 )
-					op.h_flt64.insert( op.h_flt64.end(), s.prefix_dc64,
-						s.prefix_dc64 + s.prefix_dc_len );
-			}
-			else
-			{
-				if( s.suffix_dc_len > 0 )
-					op.h_flt.insert( op.h_flt.end(), s.suffix_dc,
-						s.suffix_dc + s.suffix_dc_len );
-				if( s.prefix_dc_len > 0 )
-					op.h_flt.insert( op.h_flt.end(), s.prefix_dc,
-						s.prefix_dc + s.prefix_dc_len );
-			}
+			if( s.suffix_dc_len > 0 )
+				ot.h_flt.insert( ot.h_flt.end(), st.suffix_dc,
+					st.suffix_dc + s.suffix_dc_len );
+			if( s.prefix_dc_len > 0 )
+				ot.h_flt.insert( ot.h_flt.end(), st.prefix_dc,
+					st.prefix_dc + s.prefix_dc_len );
 
 			L.ops.push_back( op );
 			prev_upf = true;
@@ -379,8 +384,7 @@ static int lower_axis( const avirhip_axis& ax, int src_len, int dst_len,
 				return( AVIRHIP_EUNSUPPORTED );
 			}
 
-			if( s.rpos == nullptr || ( f64 ? (const void*) s.phase_taps64 :
-				(const void*) s.phase_taps ) == nullptr ||
+			if( s.rpos == nullptr || st.phase_taps == nullptr ||
 				s.bank_filter_len < 2 || s.n_phases < 1 ||
 				( s.bank_order != 0 && s.bank_order != 1 ))
 			{
@@ -395,14 +399,7 @@ static int lower_axis( const avirhip_axis& ax, int src_len, int dst_len,
 			op.h_start.resize( s.out_len );
 			op.h_ntaps.resize( s.out_len );
 
-			if( f64 )
-			{
-				op.h_coef64.assign( (size_t) s.out_len * op.maxtaps, 0.0 );
-			}
-			else
-			{
-				op.h_coef.assign( (size_t) s.out_len * op.maxtaps, 0.0f );
-			}
+			ot.h_coef.assign( (size_t) s.out_len * op.maxtaps, (F) 0.0 );
 
 			if( r2 )
 			{
@@ -425,43 +422,18 @@ static int lower_axis( const avirhip_axis& ax, int src_len, int dst_len,
 				const int stp = ( r2 ? 2 : 1 );
 				int nt = 0;
 
-				if( f64 )
+				const F* ftp = st.phase_taps + (size_t) rp.phase * fsz +
+					rp.ftp_off;
+				const F* ftp2 = ftp + fl;
+				F* cf = &ot.h_coef[ (size_t) j * op.maxtaps ];
+
+				for( int i = 0; i < rp.fl; i += stp )
 				{
-					// (the same in double: xx = ftp[i] + ftp2[i]*x)
-					const double* ftp = s.phase_taps64 + (size_t) rp.phase * fsz +
-						rp.ftp_off;
-					const double* ftp2 = ftp + fl;
-					double* cf = &op.h_coef64[ (size_t) j * op.maxtaps ];
-
-					for( int i = 0; i < rp.fl; i += stp )
-					{
-						if( s.bank_order == 1 )
-						{
-							const double t = ftp2[ i ] * rp.x64;
-							cf[ nt ] = ftp[ i ] + t;
-						}
-						else
-						{
-							cf[ nt ] = ftp[ i ];
-						}
-
-						nt++;
-					}
-				}
-
-				const float* ftp = ( f64 ? nullptr : s.phase_taps +
-					(size_t) rp.phase * fsz + rp.ftp_off );
-				const float* ftp2 = ( f64 ? nullptr : ftp + fl );
-				float* cf = ( f64 ? nullptr :
-					&op.h_coef[ (size_t) j * op.maxtaps ]);
-
-				for( int i = 0; !f64 && i < rp.fl; i += stp )
-				{
-					// xx = ftp[i] + ftp2[i]*x in float (avir.h:3945, 4177);
+					// xx = ftp[i] + ftp2[i]*x in F (avir.h:3945, 4177);
 					// this TU is compiled -ffp-contract=off.
 					if( s.bank_order == 1 )
 					{
-						const float t = ftp2[ i ] * rp.x;
+						const F t = ftp2[ i ] * rp.*st.x;
 						cf[ nt ] = ftp[ i ] + t;
 					}
 					else
@@ -534,27 +506,44 @@ static int lower_axis( const avirhip_axis& ax, int src_len, int dst_len,
 	return( AVIRHIP_OK );
 }
 
+static int lower_axis( const avirhip_axis& ax, int src_len, int dst_len,
+	LAxis& L, const bool f64 = false )
+{
+	return( f64 ? lower_axis_as< double >( ax, src_len, dst_len, L ) :
+		lower_axis_as< float >( ax, src_len, dst_len, L ));
+}
+
+// an op's filter taps of type F, with the DC tails stashed behind them
+template< typename F >
+static int upload_flt( avirhip_plan* p, LOp& op )
+{
+	const auto t = op_tab< F >( op );
+	const int rc = upload( p, t.h_flt, &t.d_flt );
+
+	if( rc == 0 && op.type == OP_UPF )
+	{
+		t.d_sdc = t.d_flt + op.flen;
+		t.d_pdc = t.d_sdc + op.sdc_len;
+	}
+
+	return( rc );
+}
+
 static int upload_axis( avirhip_plan* p, LAxis& L )
 {
 	for( size_t i = 0; i < L.ops.size(); i++ )
 	{
 		LOp& op = L.ops[ i ];
+		const auto tf = op_tab< float >( op );
+		const auto td = op_tab< double >( op );
 		int rc;
 
-		if(( rc = upload( p, op.h_flt, &op.d_flt )) != 0 ) return( rc );
+		if(( rc = upload_flt< float >( p, op )) != 0 ) return( rc );
 		if(( rc = upload( p, op.h_start, &op.d_start )) != 0 ) return( rc );
 		if(( rc = upload( p, op.h_ntaps, &op.d_ntaps )) != 0 ) return( rc );
-		if(( rc = upload( p, op.h_coef, &op.d_coef )) != 0 ) return( rc );
-		if(( rc = upload( p, op.h_flt64, &op.d_flt64 )) != 0 ) return( rc );
-		if(( rc = upload( p, op.h_coef64, &op.d_coef64 )) != 0 ) return( rc );
-
-		if( op.type == OP_UPF )
-		{
-			op.d_sdc = op.d_flt + op.flen;
-			op.d_pdc = op.d_sdc + op.sdc_len;
-			op.d_sdc64 = op.d_flt64 + op.flen;
-			op.d_pdc64 = op.d_sdc64 + op.sdc_len;
-		}
+		if(( rc = upload( p, tf.h_coef, &tf.d_coef )) != 0 ) return( rc );
+		if(( rc = upload_flt< double >( p, op )) != 0 ) return( rc );
+		if(( rc = upload( p, td.h_coef, &td.d_coef )) != 0 ) return( rc );
 	}
 
 	return( AVIRHIP_OK );
@@ -646,91 +635,102 @@ static int ensure_scratch( avirhip_plan* p )
 	return( AVIRHIP_OK );
 }
 
-static int ensure_generic_scratch( avirhip_plan* p )
+template< typename F >
+int ensure_generic_scratch( avirhip_plan* p )
 {
+	const PlanBufs< F > B = plan_bufs< F >( p );
 	int rc;
 	void* q;
 
-	if( p -> hbuf.empty() )
+	if( B.hbuf.empty() )
 	{
 		for( size_t i = 0; i < p -> h.ops.size(); i++ )
 		{
 			if(( rc = dev_alloc( p, (size_t) p -> h.ops[ i ].out_total *
-				p -> src_h * p -> ch * sizeof( float ), &q )) != 0 )
+				p -> src_h * p -> ch * sizeof( F ), &q )) != 0 )
 				return( rc );
-			p -> hbuf.push_back( (float*) q );
+			B.hbuf.push_back( (F*) q );
 		}
 
 		for( size_t i = 0; i + 1 < p -> v.ops.size(); i++ )
 		{
 			if(( rc = dev_alloc( p, (size_t) p -> v.ops[ i ].out_total *
-				p -> new_w * p -> ch * sizeof( float ), &q )) != 0 )
+				p -> new_w * p -> ch * sizeof( F ), &q )) != 0 )
 				return( rc );
-			p -> vbuf.push_back( (float*) q );
+			B.vbuf.push_back( (F*) q );
 		}
 	}
 
 	return( AVIRHIP_OK );
 }
 
-// Runs the generic chain for output rows [row0, row1) into `dst` (a float
-// surface whose row `row0` is at dst).
-static int run_generic( avirhip_plan* p, const float* src, long src_stride,
-	float* dst, int row0, int row1, hipStream_t st )
+// Backward range propagation through the vertical chain.
+VRanges v_ranges( const LAxis& v, int row0, int row1 )
 {
-	int rc = ensure_generic_scratch( p );
-	if( rc != 0 ) return( rc );
-
-	const int ch = p -> ch;
-	const int nv = (int) p -> v.ops.size();
-	const int nh = (int) p -> h.ops.size();
-
-	// Backward range propagation through the vertical chain.
-	std::vector< int > va( nv ), vb( nv );
+	const int nv = (int) v.ops.size();
+	VRanges R;
+	R.va.resize( nv ); R.vb.resize( nv );
 	int a = row0, b = row1 - 1;
 
 	for( int i = nv - 1; i >= 0; i-- )
 	{
-		const LOp& op = p -> v.ops[ i ];
-		va[ i ] = a;
-		vb[ i ] = b;
+		const LOp& op = v.ops[ i ];
+		R.va[ i ] = a;
+		R.vb[ i ] = b;
 
 		if( op.type == OP_UPF )
 		{
-			va[ i ] = -op.out_prefix;
-			vb[ i ] = op.out_total - op.out_prefix - 1;
+			R.va[ i ] = -op.out_prefix;
+			R.vb[ i ] = op.out_total - op.out_prefix - 1;
 		}
 
 		int ia, ib;
-		need_range( op, va[ i ], vb[ i ], ia, ib );
+		need_range( op, R.va[ i ], R.vb[ i ], ia, ib );
 		a = ia;
 		b = ib;
 	}
 
-	const int ya = a, yb = b; // FltBuf rows needed
+	R.ya = a; R.yb = b; // FltBuf rows needed
+	return( R );
+}
+
+// Runs the generic chain for output rows [row0, row1) into `dst` (a surface
+// of F whose row `row0` is at dst).
+template< typename F >
+int run_generic( avirhip_plan* p, const F* src, long src_stride, F* dst,
+	int row0, int row1, hipStream_t st )
+{
+	int rc = ensure_generic_scratch< F >( p );
+	if( rc != 0 ) return( rc );
+
+	const PlanBufs< F > B = plan_bufs< F >( p );
+	const int ch = p -> ch;
+	const int nv = (int) p -> v.ops.size();
+	const int nh = (int) p -> h.ops.size();
+	const VRanges R = v_ranges( p -> v, row0, row1 );
 
 	// Horizontal pass over source rows [ya, yb].
-	Surf in;
-	in.base = (float*) src; in.scan_stride = src_stride; in.idx_stride = ch;
+	Surf< F > in;
+	in.base = (F*) src; in.scan_stride = src_stride; in.idx_stride = ch;
 	in.prefix = 0;
 
 	for( int i = 0; i < nh; i++ )
 	{
 		const LOp& op = p -> h.ops[ i ];
-		Surf out;
-		out.base = p -> hbuf[ i ];
+		Surf< F > out;
+		out.base = B.hbuf[ i ];
 		out.scan_stride = (long) op.out_total * ch;
 		out.idx_stride = ch;
 		out.prefix = op.out_prefix;
 
-		if(( rc = launch_op( op, ch, true, in, out, ya, yb + 1, 0,
+		if(( rc = launch_op( op, ch, true, in, out, R.ya, R.yb + 1, 0,
 			op.out_len, st )) != 0 ) return( rc );
 
 		in = out;
 	}
 
 	// Vertical pass: scanlines are the NewWidth columns of FltBuf.
-	in.base = p -> hbuf[ nh - 1 ];
+	in.base = B.hbuf[ nh - 1 ];
 	in.scan_stride = ch;
 	in.idx_stride = (long) p -> new_w * ch;
 	in.prefix = 0;
@@ -738,7 +738,7 @@ static int run_generic( avirhip_plan* p, const float* src, long src_stride,
 	for( int i = 0; i < nv; i++ )
 	{
 		const LOp& op = p -> v.ops[ i ];
-		Surf out;
+		Surf< F > out;
 		out.scan_stride = ch;
 		out.idx_stride = (long) p -> new_w * ch;
 		out.prefix = op.out_prefix;
@@ -749,11 +749,11 @@ static int run_generic( avirhip_plan* p, const float* src, long src_stride,
 		}
 		else
 		{
-			out.base = p -> vbuf[ i ];
+			out.base = B.vbuf[ i ];
 		}
 
-		if(( rc = launch_op( op, ch, false, in, out, 0, p -> new_w, va[ i ],
-			vb[ i ] + 1, st )) != 0 ) return( rc );
+		if(( rc = launch_op( op, ch, false, in, out, 0, p -> new_w,
+			R.va[ i ], R.vb[ i ] + 1, st )) != 0 ) return( rc );
 
 		in = out;
 	}
@@ -1640,6 +1640,11 @@ static int exec_device( avirhip_plan* p, const void* src, void* dst,
 	return( p -> is_lancir ? exec_lancir( p, src, dst, row0, row1, st, win ) :
 		exec_avir( p, src, dst, row0, row1, st, win ));
 }
+
+// the per-op executor of the double pipeline (generic64.hip: exec_f64)
+template int ensure_generic_scratch< double >( avirhip_plan* );
+template int run_generic< double >( avirhip_plan*, const double*, long,
+	double*, int, int, hipStream_t );
 
 } // namespace avirhip
 

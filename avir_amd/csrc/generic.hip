@@ -6,9 +6,9 @@
 // every global access of a wave is one contiguous segment; no transposition
 // (the reference's convertVtoH, avir.h:3085-3136) is ever needed.
 //
-// Arithmetic contract (compiled -ffp-contract=off): separate v_mul_f32 /
-// v_add_f32 in the reference's order, sums started from +0.0f -- the result
-// is bit-identical to the reference's scalar float path.
+// Arithmetic contract (compiled -ffp-contract=off): separate v_mul / v_add in
+// the reference's order, sums started from +0.0 -- bit-identical to the
+// reference's scalar path, in float and, with F = double, double.
 
 #include "plan.h"
 #include <atomic>
@@ -19,21 +19,21 @@
 
 namespace avirhip {
 
-struct OpArgs
+template< typename F > struct OpArgs
 {
-	const float* in; long in_ss, in_is; int in_prefix;
-	float* out; long out_ss, out_is; int out_prefix;
+	const F* in; long in_ss, in_is; int in_prefix;
+	F* out; long out_ss, out_is; int out_prefix;
 	int view, in_len, zs_mmax;
 	int ch;
 	int scan0, nscan, idx0, nidx;
-	int rf, lat, e; const float* flt;
-	const int* start; const int* ntaps; const float* coef; int maxtaps;
+	int rf, lat, e; const F* flt;
+	const int* start; const int* ntaps; const F* coef; int maxtaps;
 	int flen, up_inprefix, up_R, sdc_len, pdc_len, pdc_d0;
-	const float* sdc; const float* pdc;
+	const F* sdc; const F* pdc;
 };
 
-__device__ __forceinline__ float ldv( const OpArgs& a, const long so, int i,
-	const int c )
+template< typename F >
+__device__ __forceinline__ F ldv( const OpArgs< F >& a, long so, int i, int c )
 {
 	if( a.view == VIEW_RAW )
 	{
@@ -42,7 +42,7 @@ __device__ __forceinline__ float ldv( const OpArgs& a, const long so, int i,
 
 	if( a.view == VIEW_ZS && i > a.zs_mmax )
 	{
-		return( 0.0f );
+		return( (F) 0.0 );
 	}
 
 	i = ( i < 0 ? 0 : ( i >= a.in_len ? a.in_len - 1 : i ));
@@ -50,8 +50,8 @@ __device__ __forceinline__ float ldv( const OpArgs& a, const long so, int i,
 }
 
 // Thread (x, y): XIDX ? (idx, scan) : (scan, idx). x is always along image x.
-template< bool XIDX >
-__device__ __forceinline__ bool locate( const OpArgs& a, int& scan, int& idx )
+template< bool XIDX, typename A > // (A: an OpArgs< F >)
+__device__ __forceinline__ bool locate( const A& a, int& scan, int& idx )
 {
 	const int x = blockIdx.x * blockDim.x + threadIdx.x;
 	const int y = blockIdx.y * blockDim.y + threadIdx.y;
@@ -69,8 +69,8 @@ __device__ __forceinline__ bool locate( const OpArgs& a, int& scan, int& idx )
 }
 
 // doFilter, avir.h:3748-3866.
-template< bool XIDX >
-__global__ void __launch_bounds__( 256 ) k_fir( const OpArgs a )
+template< typename F, bool XIDX >
+__global__ void __launch_bounds__( 256 ) k_fir( const OpArgs< F > a )
 {
 	int scan, n;
 
@@ -85,7 +85,7 @@ __global__ void __launch_bounds__( 256 ) k_fir( const OpArgs a )
 
 	for( int c = 0; c < a.ch; c++ )
 	{
-		float s = a.flt[ 0 ] * ldv( a, so, cp, c );
+		F s = a.flt[ 0 ] * ldv( a, so, cp, c );
 
 		for( int i = 1; i <= a.lat; i++ )
 		{
@@ -98,8 +98,8 @@ __global__ void __launch_bounds__( 256 ) k_fir( const OpArgs a )
 }
 
 // doResize / doResize2, avir.h:3884-4328 (coefficients pre-expanded).
-template< bool XIDX >
-__global__ void __launch_bounds__( 256 ) k_gather( const OpArgs a )
+template< typename F, bool XIDX >
+__global__ void __launch_bounds__( 256 ) k_gather( const OpArgs< F > a )
 {
 	int scan, j;
 
@@ -112,11 +112,11 @@ __global__ void __launch_bounds__( 256 ) k_gather( const OpArgs a )
 	const long oo = (long) scan * a.out_ss + (long) j * a.out_is;
 	const int st = a.start[ j ];
 	const int nt = a.ntaps[ j ];
-	const float* cf = a.coef + (long) j * a.maxtaps;
+	const F* cf = a.coef + (long) j * a.maxtaps;
 
 	for( int c = 0; c < a.ch; c++ )
 	{
-		float sum = 0.0f;
+		F sum = 0.0;
 
 		for( int t = 0; t < nt; t++ )
 		{
@@ -127,12 +127,11 @@ __global__ void __launch_bounds__( 256 ) k_gather( const OpArgs a )
 	}
 }
 
-// doUpsample with filtering, avir.h:3404-3733, as a gather over the
-// destination slot d = idx + OutPrefix. Contributions arrive in ascending
-// input order, then the SuffixDC tail, then the PrefixDC tail -- the order in
-// which the reference's scatter-adds touch the slot.
-template< bool XIDX >
-__global__ void __launch_bounds__( 256 ) k_upf( const OpArgs a )
+// doUpsample with filtering, avir.h:3404-3733, as a gather over the slot
+// d = idx + OutPrefix. Contributions arrive in ascending input order, then the
+// SuffixDC and the PrefixDC tail: the order of the reference's scatter-adds.
+template< typename F, bool XIDX >
+__global__ void __launch_bounds__( 256 ) k_upf( const OpArgs< F > a )
 {
 	int scan, d;
 
@@ -157,7 +156,7 @@ __global__ void __launch_bounds__( 256 ) k_upf( const OpArgs a )
 
 	for( int c = 0; c < a.ch; c++ )
 	{
-		float s = 0.0f;
+		F s = 0.0;
 
 		for( int r = rlo; r <= rhi; r++ )
 		{
@@ -181,11 +180,12 @@ __global__ void __launch_bounds__( 256 ) k_upf( const OpArgs a )
 	}
 }
 
-int launch_op( const LOp& op, int ch, bool x_is_idx, const Surf& in,
-	const Surf& out, int scan0, int scan1, int idx0, int idx1,
+template< typename F >
+int launch_op( const LOp& op, int ch, bool x_is_idx, const Surf< F >& in,
+	const Surf< F >& out, int scan0, int scan1, int idx0, int idx1,
 	hipStream_t st )
 {
-	OpArgs a;
+	OpArgs< F > a;
 	a.in = in.base; a.in_ss = in.scan_stride; a.in_is = in.idx_stride;
 	a.in_prefix = in.prefix;
 	a.out = out.base + (long) out.prefix * out.idx_stride;
@@ -195,12 +195,12 @@ int launch_op( const LOp& op, int ch, bool x_is_idx, const Surf& in,
 	a.ch = ch;
 	a.scan0 = scan0; a.nscan = scan1 - scan0;
 	a.idx0 = idx0; a.nidx = idx1 - idx0;
-	a.rf = op.rf; a.lat = op.lat; a.e = op.e; a.flt = op.d_flt;
-	a.start = op.d_start; a.ntaps = op.d_ntaps; a.coef = op.d_coef;
-	a.maxtaps = op.maxtaps;
+	a.rf = op.rf; a.lat = op.lat; a.e = op.e; a.flt = op_tab< F >( op ).d_flt;
+	a.start = op.d_start; a.ntaps = op.d_ntaps; a.maxtaps = op.maxtaps;
+	a.coef = op_tab< F >( op ).d_coef;
 	a.flen = op.flen; a.up_inprefix = op.up_inprefix; a.up_R = op.up_R;
 	a.sdc_len = op.sdc_len; a.pdc_len = op.pdc_len; a.pdc_d0 = op.pdc_d0;
-	a.sdc = op.d_sdc; a.pdc = op.d_pdc;
+	a.sdc = op_tab< F >( op ).d_sdc; a.pdc = op_tab< F >( op ).d_pdc;
 
 	if( op.type == OP_UPF )
 	{
@@ -220,8 +220,8 @@ int launch_op( const LOp& op, int ch, bool x_is_idx, const Surf& in,
 	const int ny = ( x_is_idx ? a.nscan : a.nidx );
 	const dim3 grd(( nx + 63 ) / 64, ( ny + 3 ) / 4 );
 
-#define LAUNCH( K ) if( x_is_idx ) hipLaunchKernelGGL( K< true >, grd, blk, 0, \
-		st, a ); else hipLaunchKernelGGL( K< false >, grd, blk, 0, st, a )
+#define LAUNCH( K ) hipLaunchKernelGGL(( x_is_idx ? K< F, true > : \
+		K< F, false > ), grd, blk, 0, st, a )
 
 	if( op.type == OP_FIR ) { LAUNCH( k_fir ); }
 	else if( op.type == OP_GATHER ) { LAUNCH( k_gather ); }
@@ -2351,6 +2351,12 @@ int launch_lancir_out( const avirhip_plan* p, const float* res, long rstride,
 	AVIRHIP_HIPCHECK( hipGetLastError() );
 	return( AVIRHIP_OK );
 }
+
+// the per-op executor in its two working types (api.cpp, generic64.hip)
+template int launch_op< float >( const LOp&, int, bool, const Surf< float >&,
+	const Surf< float >&, int, int, int, int, hipStream_t );
+template int launch_op< double >( const LOp&, int, bool, const Surf< double >&,
+	const Surf< double >&, int, int, int, int, hipStream_t );
 
 } // namespace avirhip
 

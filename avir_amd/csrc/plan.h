@@ -78,8 +78,7 @@ struct LOp
 	int rf, lat, e;
 	float* d_flt; // FIR: &Flt[FltLatency] (lat+1 taps); UPF: whole Flt
 	std::vector< float > h_flt;
-	// (double pipeline, plan -> f64: the same tables in double; the float ones
-	// stay empty)
+	// (plan -> f64: the same tables in double, and the float ones stay empty)
 	double* d_flt64;
 	std::vector< double > h_flt64;
 
@@ -111,9 +110,10 @@ struct LAxis
 
 // Image element access: address(scan, idx, c) =
 //   base + scan*scan_stride + (idx + prefix)*idx_stride + c
+template< typename F >
 struct Surf
 {
-	float* base;
+	F* base;
 	long scan_stride;
 	long idx_stride;
 	int prefix;
@@ -368,6 +368,56 @@ int finalize_avir_plan( avirhip_plan* p ); // api.cpp
 // other-device replicas (the plan caches' byte bound)
 size_t plan_device_bytes( avirhip_plan* p );
 
+// ---- the float and the double tables of one plan, chosen by working type ----
+
+// The tables of an op in the working type F (float, or double for a plan -> f64
+// plan), whichever way the op is held: every reader that is written for both
+// types -- lowering, upload, the per-op executor -- names them through here.
+template< typename V, typename P >
+struct OpTab
+{
+	V h_flt; P d_flt;
+	V h_coef; P d_coef;
+	P d_sdc; P d_pdc;
+};
+
+template< typename F, typename L > // (L: LOp or const LOp)
+inline auto op_tab( L& op )
+{
+	if constexpr( sizeof( F ) == sizeof( double ))
+	{
+		return( OpTab< decltype(( op.h_flt64 )), decltype(( op.d_flt64 )) >{
+			op.h_flt64, op.d_flt64, op.h_coef64, op.d_coef64, op.d_sdc64,
+			op.d_pdc64 });
+	}
+	else
+	{
+		return( OpTab< decltype(( op.h_flt )), decltype(( op.d_flt )) >{
+			op.h_flt, op.d_flt, op.h_coef, op.d_coef, op.d_sdc, op.d_pdc });
+	}
+}
+
+// The per-op executor's intermediates in the working type F (see op_tab)
+template< typename F >
+struct PlanBufs
+{
+	std::vector< F* >& hbuf;
+	std::vector< F* >& vbuf;
+};
+
+template< typename F >
+inline PlanBufs< F > plan_bufs( avirhip_plan* p )
+{
+	if constexpr( sizeof( F ) == sizeof( double ))
+	{
+		return( PlanBufs< F >{ p -> hbuf64, p -> vbuf64 });
+	}
+	else
+	{
+		return( PlanBufs< F >{ p -> hbuf, p -> vbuf });
+	}
+}
+
 // generic.hip
 // `ch` = channels in `src`, `ech` >= ch = channels written (zero padded)
 int launch_pack( const void* src, int in_type, float* dst, int w, int h,
@@ -376,8 +426,11 @@ int launch_pack_gamma( const void* src, int in_type, float* dst, int w, int h,
 	int ch, int ech, long src_stride, int alpha_index, const float* tbl,
 	hipStream_t st );
 void srgb_u8_table( float* tbl );
-int launch_op( const LOp& op, int ch, bool x_is_idx, const Surf& in,
-	const Surf& out, int scan0, int scan1, int idx0, int idx1,
+// one lowered op in the working type F (float, double): outputs [idx0, idx1)
+// of scanlines [scan0, scan1)
+template< typename F >
+int launch_op( const LOp& op, int ch, bool x_is_idx, const Surf< F >& in,
+	const Surf< F >& out, int scan0, int scan1, int idx0, int idx1,
 	hipStream_t st );
 int launch_epilogue( const float* res, void* dst, int out_type, long n,
 	double tr_mul, double pk_out, int gamma, int ch, int ech,
@@ -387,6 +440,22 @@ bool gamma_u8_thresholds( float ogm, int use_tr, float trm, float trmi,
 	float pk, float* thr );
 // the input range [ia, ib] an op reads for outputs [a, b] (api.cpp)
 void need_range( const LOp& op, int a, int b, int& ia, int& ib );
+// the outputs [va[ i ], vb[ i ]] each op of a plan's vertical chain makes for
+// output rows [row0, row1), and the FltBuf rows [ya, yb] the first one reads
+struct VRanges
+{
+	std::vector< int > va, vb;
+	int ya, yb;
+};
+VRanges v_ranges( const LAxis& v, int row0, int row1 ); // api.cpp
+// the per-op executor (api.cpp): its intermediates, and the chain of a plan for
+// output rows [row0, row1) into `dst` (a surface of F whose row `row0` is at
+// dst), float plans in float, plan -> f64 plans in double
+template< typename F >
+int ensure_generic_scratch( avirhip_plan* p );
+template< typename F >
+int run_generic( avirhip_plan* p, const F* src, long src_stride, F* dst,
+	int row0, int row1, hipStream_t st );
 // the source rows [*first, *last] the outputs [row0, row1) of a lowered axis
 // read; the same from a plan description's vertical axis (host only)
 void axis_src_range( const LAxis& ax, int row0, int row1, int src_len,

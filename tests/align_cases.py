@@ -477,8 +477,8 @@ _row("tile64_f64", ["tile64.hip"], "avir", (400, 600, 250, 375), F64C4, 0, 0,
      ex=dict(F.DBL, auto_path=2))
 _row("generic64_f32c3", ["generic64.hip"], "avir", (400, 600, 250, 375),
      dict(ch=3, tin="f32", tout="f32", bits=16), 1, 0, None,
-     _s(*[_elem(4, "generic64.hip:91", "const long so = (long) scan * "
-                "a.in_ss;")] * 3), N_64, ex=dict(F.DBL))
+     _s(*[_elem(4, "generic64.hip:72", "const Tin v = src[ (long) y * "
+                "src_stride + px * ch + c ];")] * 3), N_64, ex=dict(F.DBL))
 _Q_VST = "( (uintptr_t) dst % ( 2 * osz )) == 0 ? 1 : 0 );"
 _Q_U64 = "const Tin* const sp = (const Tin*) P.src + (long) row * P.src_ss;"
 _row("up64_f32c3_f64", ["up64.hip"], "avir", (200, 400, 400, 800),

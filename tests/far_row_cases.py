@@ -300,8 +300,8 @@ _row("tile64_f64", ["tile64.hip"], "avir", (400, 600, 250, 375),
            "(long) ( row_lo + y ) *"), N_64, ex=dict(DBL, auto_path=2))
 _row("generic64_f32c3", ["generic64.hip"], "avir", (400, 600, 250, 375),
      dict(ch=3, tin="f32", tout="f32", bits=16), 1, 0,
-     _none("generic64.hip:91", "const long so = (long) scan * a.in_ss;"),
-     N_64, ex=dict(DBL))
+     _none("generic64.hip:72", "const Tin v = src[ (long) y * src_stride + "
+           "px * ch + c ];"), N_64, ex=dict(DBL))
 _row("up64_f32c3_f64", ["up64.hip"], "avir", (200, 400, 400, 800),
      dict(ch=3, tin="f32", tout="f64", bits=16), 0, 0,
      _none("up64.hip:143", "const Tin* const sp = (const Tin*) P.src + "
