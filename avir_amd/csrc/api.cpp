@@ -1185,6 +1185,49 @@ static bool avir_dn_stores( const RoadCall& C )
 		fused_stores_int( C.p, C.path ));
 }
 
+// Path 4 with sRGB gamma: the marching kernel de-linearises and stores a uint8
+// result itself (k_up2's IO 8 / 9; up2_stores_io has the plan's conditions).
+// AVIRHIP_VARIANT_UP2_UNFUSED_IO and AVIRHIP_NO_FUSED_OUT: the pack pass, the
+// float kernel and the output stage, as before these kinds.
+static bool up2_gamma_stores( const RoadCall& C )
+{
+	return( C.path == 4 && C.p -> gamma && !C.direct && avir_fio( C ) &&
+		up2_stores_io( C.p ));
+}
+
+// The kernel's gamma kinds search the thresholds a row pair at a time (eight
+// dependent LDS gathers for a lane's four values), which makes their vertical
+// phase about three times the plain kernel's and bound by that latency, where
+// the output stage of the road before runs the search at full occupancy. The
+// one launch is faster only where the three launches' float traffic outweighs
+// that and the frame still fills the chip. Both sides fused (uint8 RGB(A) read
+// raw): frames of up2srgb_raw_minpix() to up2srgb_raw_maxpix() source pixels
+// (faster at 2,073,600, slower at 921,600 and at 3,686,400: between them the
+// interpolated crossings, rounded inwards). The store side alone (the pack
+// pass in front) was faster at no size: up to up2srgb_store_maxpix() pixels,
+// none by default. AVIRHIP_UP2SRGB_RAW_MINPIX, AVIRHIP_UP2SRGB_RAW_MAXPIX and
+// AVIRHIP_UP2SRGB_STORE_MAXPIX, read per call; NOTEBOOK section 34.
+static long up2srgb_raw_minpix()
+{
+	const char* const e = getenv( "AVIRHIP_UP2SRGB_RAW_MINPIX" );
+
+	return( e != nullptr ? atol( e ) : 1700000L );
+}
+
+static long up2srgb_raw_maxpix()
+{
+	const char* const e = getenv( "AVIRHIP_UP2SRGB_RAW_MAXPIX" );
+
+	return( e != nullptr ? atol( e ) : 2700000L );
+}
+
+static long up2srgb_store_maxpix()
+{
+	const char* const e = getenv( "AVIRHIP_UP2SRGB_STORE_MAXPIX" );
+
+	return( e != nullptr ? atol( e ) : 0L );
+}
+
 // The store side of k_dnfh's sRGB kinds ALONE (a source the kernel cannot
 // read: the pack pass in front of k_dnfh< F32, S8 >) saves the output stage's
 // launch and the float result, and pays for the threshold search in the column
@@ -1220,8 +1263,12 @@ static long dnsrgb_store_maxpix()
 //   tiles          2, 3   RAW integer pixels | STORE: avir_dn_stores     k_tile / k_dnf,
 //                                                                        dn passes
 //   k_up2 raw      4      RAW + STORE: integer RGB(A) or 16-bit RGBA on  k_up2
-//                         both sides, up2_stores_io
-//   k_up2 store    4      FLOAT + STORE: avir_stores                     k_up2
+//                         both sides, up2_stores_io; with gamma uint8
+//                         RGB(A) on both sides (the kernel's sRGB kinds),
+//                         up2srgb_raw_minpix() to _maxpix() pixels
+//   k_up2 store    4      FLOAT + STORE: avir_stores; with gamma a uint8  k_up2
+//                         result that up2_stores_io takes (up2_gamma_stores)
+//                         up to up2srgb_store_maxpix() pixels
 //   k_up2          4      FLOAT + FLOAT                                  k_up2
 //   pass store     5      STORE: avir_stores; RAW as below               gpass_route's
 //   pass           5      RAW integer / float / 16-bit (`raw16`) pixels  gpass_route's
@@ -1233,7 +1280,8 @@ static long dnsrgb_store_maxpix()
 //
 // `lazy`: the call skips ensure_scratch and allocates `packed` and `resbuf`
 // only when an attempt is about to use them -- k_dnfh's two roads, taken or
-// not, and the pass kernels with 16-bit pixels on a side. `first`: what the
+// not, k_up2's gamma road, and the pass kernels with 16-bit pixels on a side.
+// `first`: what the
 // tiles behind k_dnfh, refused or never listed, ask of the plan before they
 // make their sides ready: behind the sRGB kinds the float copies their road
 // expects to find (ensure_scratch), behind the 16-bit kinds `resbuf` -- also
@@ -1321,8 +1369,20 @@ static Road avir_road( const RoadCall& C )
 	// (nor does a call of the pass kernels with 16-bit pixels on a side, whose
 	// first pass may read and whose last pass may store them, make its float
 	// copies up front)
-	R.lazy = ( srgb || dn16 || ( path == 5 && !p -> gamma && gpass_io16() &&
-		( h_in || h_out )));
+	// (nor does the marching kernel's gamma road: a uint8 call that the raw kind
+	// completes holds neither copy)
+	// (with gamma: a uint8 RGB(A) image through the linearising table and the
+	// uint8 result through the thresholds; or the thresholds alone)
+	const long up2g_px = (long) p -> src_w * p -> src_h;
+	const bool up2g_any = up2_gamma_stores( C );
+	const bool up2g_raw = ( up2g_any && p -> ch == 4 &&
+		p -> in_type == AVIRHIP_U8 && p -> d_srgb_tbl != nullptr &&
+		up2g_px >= up2srgb_raw_minpix() && up2g_px <= up2srgb_raw_maxpix());
+	const bool up2g_store = ( up2g_any && up2g_px <= up2srgb_store_maxpix());
+	const bool up2g = ( up2g_raw || up2g_store );
+
+	R.lazy = ( srgb || dn16 || up2g || ( path == 5 && !p -> gamma &&
+		gpass_io16() && ( h_in || h_out )));
 
 	// integer / narrower sources: the path's first kernel reads the caller's
 	// image as it lies, the float copy of the source (pack pass) is skipped --
@@ -1343,9 +1403,12 @@ static Road avir_road( const RoadCall& C )
 		// kernel reads the elements as they lie
 		const bool half_io = ( h_in && p -> out_type == p -> in_type &&
 			p -> io_ch == 4 );
-		const bool stores = avir_stores( C );
+		const bool stores = ( avir_stores( C ) || up2g_store );
 
-		if( stores && raw_ok && C.need_pack && (( int_in &&
+		// (up2g_raw: up2_stores_io, the default ditherer and avir_fio hold;
+		// up2_run may still refuse -- a source window, AVIRHIP_UP2_NO_RAW: the
+		// next row, or the road before when the store side alone is not offered)
+		if(( up2g_raw || ( stores && raw_ok )) && C.need_pack && (( int_in &&
 			( p -> io_ch == 3 || p -> io_ch == 4 ) &&
 			dtype_is_int( p -> out_type )) || half_io ) &&
 			p -> dither == AVIRHIP_DITHER_DEF && up2_stores_io( p ) &&

@@ -40,6 +40,7 @@
 
 #include "plan.h"
 #include "up2_chunks.h"
+#include "up2_params.h"
 #include <algorithm>
 #include <string.h>
 #include <stdlib.h>
@@ -65,26 +66,9 @@ typedef unsigned u2 __attribute__(( ext_vector_type( 2 )));
 #define U2_SW ( U2_TW / 2 + 18 ) // S tile width (px)
 #define U2_CW ( U2_TW / 2 + 12 ) // C tile width (px)
 
-struct Up2Params
-{
-	const float* src; long src_ss; int sw, sh;
-	int rmin, rmax; // source rows that exist behind `src` (a window: plan.h)
-	float* dst; long dst_ss; int dst_row0; int nw, nh;
-	int srow_lo, srow_hi;
-	int nstrips, chunk0, nchunks;
-	int cq, nlong; // source rows (output row pairs) per chunk: the first nlong
-		// chunks of a strip hold cq + U2_RB, the others cq (up2_chunks.h)
-	// IO != 0: the caller's image instead of dst -- uint8 / uint16 (the output
-	// stage of dither(), avir.h:4392-4419, without bit-depth truncation) or
-	// float pixels of 1-3 channels; ibase = the band's first row
-	void* ibase; int istride_b; int ich;
-#ifdef U2_DBG
-	int dbg; // timing ablations (debug build only)
-	unsigned long long* clk; // [items][4]: shader cycles, start, end (100 MHz ticks), hw id
-#endif
-	const float* coef; // device: the taps, horizontal axis first, packed
-		// (2 x 32 floats) and paired (2 x 64 from U2_PAIRED): see Taps
-};
+// (Up2Params, the kernel's parameters, and Up2GParams, which the sRGB gamma
+// kinds take instead: up2_params.h. tests/align_cases.py, tests/far_row_cases.py
+// and DESIGN's alignment tables quote lines of this file by number.)
 
 // The 28 wave-uniform filter taps of one axis, in two layouts (up2_prepare):
 //   packed (the transposed form, k_up2< true >): ONE float per tap,
@@ -332,9 +316,25 @@ __device__ __forceinline__ void u2_setprio( const int p )
 // exactly (v_cvt_f32_f16, denormals kept) instead of cast from integers.
 // 200 + such a code (224: bfloat16 RGBA): the elements are upper halves of
 // floats -- a shift and a mask per dword, no conversion.
+// sRGB gamma (UseSRGBGamma) with 8-bit pixels, the stages of generic.hip's pack
+// pass and output stage inside this launch (expressions: dnsrgb_dev.h; the
+// parameters: Up2GParams):
+// SRC 313 / 314: uint8 RGB / RGBA read as 13 / 14 are, linearised in land_raw --
+// a colour channel is tbl[ byte ] from a workgroup LDS copy of the plan's
+// 256-entry table, the alpha channel (float) byte * gm.
+// IO 8: a uint8 result through the de-linearising stage: a channel's byte is the
+// count of thresholds thr[ 1..255 ] <= v (k_epilogue_gamma_thr's eight compares
+// over the colour or the alpha half of an LDS copy of the plan's 2 x 256
+// thresholds); a value outside |v| <= 16 takes that kernel's direct branch.
+// IO 9: the same behind a uint8 / uint16 source, without the direct branch (the
+// bound: store_g). Their parameters: Up2GParams, and the kernel's own at
+// the same kernel-argument offsets; the kinds without gamma are unchanged
+// machine code.
+// LDS: the 2 KB of thresholds leave seven workgroups a CU, with the 1 KB table
+// of SRC 313 / 314 six (three waves a SIMD: what the attribute below says).
 template< bool VT, int IO = 0, int SRC = 0 >
-__global__ void __launch_bounds__( U2_NT )
-__attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
+__global__ void __launch_bounds__( U2_NT ) __attribute__((
+	amdgpu_waves_per_eu( SRC / 100 == 3 ? 3 : 4, 4 ))) k_up2( const Up2PT< IO > P )
 {
 	static_assert( IO == 0 || VT, "the fused output stage lives in the VT form" );
 	static_assert( SRC == 0 || VT, "raw sources live in the VT form" );
@@ -347,7 +347,7 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 	constexpr int PXB = ( SRC != 0 ? SESZ * SCH : 16 ); // bytes per source pixel
 	// (IO 4 / 5: uint8 / uint16 results of an INTEGER source -- finite and far
 	// inside the int range, so the stage is add, convert, integer clamp)
-	constexpr int ESZ = ( IO == 1 || IO == 4 ? 1 :
+	constexpr int ESZ = ( IO == 1 || IO == 4 || up2_gamma_out< IO > ? 1 :
 		( IO == 2 || IO == 5 || IO == 6 || IO == 7 ? 2 : 4 ));
 	// LDS tiles, whole pixels (16 B). The horizontal phases work on whole
 	// pixels so that every LDS access is a conflict-free 128-bit one; the
@@ -436,6 +436,11 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 	const __amdgpu_buffer_rsrc_t rdst = __builtin_amdgcn_make_buffer_rsrc(
 		(void*) ( P.dst + (long) ( qy0 * 2 - P.dst_row0 ) * P.dst_ss ), 0,
 		0x7fffffff, 0x00020000 );
+
+	constexpr bool GSRC = ( SRC / 100 == 3 ); // raw uint8 elements, linearised
+	constexpr bool GOUT = up2_gamma_out< IO >; // a de-linearised uint8 result
+	static_assert( !GSRC || ( SESZ == 1 && GOUT ),
+		"a linearised source is uint8, its result de-linearised" );
 
 	f2 tw[ 8 ];  // ring of the last T values of this column   (slot u & 7)
 	f2 cw[ VT ? 1 : 16 ]; // ring of the last C2 values of this column (slot u & 15)
@@ -631,6 +636,24 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 						(unsigned short) ( hi & 0xffffu ));
 					px.w = ( SCH == 4 ? (float) __builtin_bit_cast( _Float16,
 						(unsigned short) ( hi >> 16 )) : 0.0f );
+				}
+				else
+				if constexpr( GSRC )
+				{
+					// (k_pack_gamma_px< uint8_t, SCH >'s expressions)
+					const float* const tbl = ds_table< 256 >();
+					const unsigned b0 = lo & 0xffu, b3 = lo >> 24;
+					px.x = tbl[ b0 ];
+					px.y = tbl[ ( lo >> 8 ) & 0xffu ];
+					px.z = tbl[ ( lo >> 16 ) & 0xffu ];
+					px.w = 0.0f;
+
+					if constexpr( SCH == 4 )
+					{
+						px.w = tbl[ b3 ];
+						px.x = ( P.G.alpha_index == 0 ? (float) b0 * P.G.gm : px.x );
+						px.w = ( P.G.alpha_index == 3 ? (float) b3 * P.G.gm : px.w );
+					}
 				}
 				else
 				if( SESZ == 1 )
@@ -1089,8 +1112,30 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 
 	prefetch( u0 );
 
+	// the gamma kinds' tables: the plan's, copied by the workgroup's threads
+	if constexpr( GSRC )
+	{
+		for( int i = tid; i < 256; i += U2_NT )
+		{
+			ds_table< 256 >()[ i ] = P.G.tbl[ i ];
+		}
+	}
+
+	if constexpr( GOUT )
+	{
+		for( int i = tid; i < U2_GTHR; i += U2_NT )
+		{
+			ds_table< U2_GTHR >()[ i ] = P.G.thr[ i ];
+		}
+	}
+
 	if constexpr( SRC != 0 )
 	{
+		if constexpr( GSRC )
+		{
+			U2_SYNC(); // (the first tile's conversion reads the whole table)
+		}
+
 		AVIRHIP_WAIT_VM( 0 );
 		land_raw( u0 );
 	}
@@ -1150,97 +1195,8 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 			(long) ( qy0 * 2 - P.dst_row0 ) * P.istride_b ) :
 			(void*) ( P.dst + (long) ( qy0 * 2 - P.dst_row0 ) * P.dst_ss ));
 
-		// IO != 0: a lane's two channels through the output stage (round
-		// half up by truncation, clamp; the x86 build's cast beyond the int
-		// range: plan.h) into the caller's image
-		auto store_io = [&]( const f2 v, const __amdgpu_buffer_rsrc_t rs,
-			const int soff )
-		{
-			if constexpr( IO == 7 )
-			{
-				// (a plain conversion of the pair, ONE v_cvt_pk_bf16_f32: nearest
-				// even, float denormals become bfloat16 denormals, beyond the
-				// largest finite one +-Inf)
-				typedef __bf16 bf2 __attribute__(( ext_vector_type( 2 )));
-				__builtin_amdgcn_raw_buffer_store_b32( __builtin_bit_cast(
-					unsigned, __builtin_convertvector( v, bf2 )), rs, dlv, soff,
-					U2_STAUX );
-			}
-			else
-			if constexpr( IO == 6 )
-			{
-				// (plain conversions: v_cvt_f16_f32 rounds to nearest even and
-				// keeps half denormals; the pkrtz form would truncate)
-				const float v0 = v.x, v1 = v.y;
-				const unsigned h0 = __builtin_bit_cast( unsigned short,
-					(_Float16) v0 );
-				const unsigned h1 = __builtin_bit_cast( unsigned short,
-					(_Float16) v1 );
-				__builtin_amdgcn_raw_buffer_store_b32( h0 | ( h1 << 16 ), rs, dlv,
-					soff, U2_STAUX );
-			}
-			else
-			if constexpr( IO == 3 )
-			{
-				// (element by element: __builtin_bit_cast of `v.y` stored v.x)
-				const float v0 = v.x, v1 = v.y;
-				__builtin_amdgcn_raw_buffer_store_b32( __float_as_uint( v0 ), rs,
-					dlv, soff, U2_STAUX );
-				__builtin_amdgcn_raw_buffer_store_b32( __float_as_uint( v1 ), rs,
-					dlv2, soff, U2_STAUX );
-			}
-			else
-			if constexpr( IO == 4 || IO == 5 )
-			{
-				// (float) (int) ( v + 0.5f ), clamped to [0, PK], cast: the same
-				// number as the integer ( v + 0.5f ) truncates to, clamped --
-				// for every |v| < 2^31, and an integer image's results are
-				// within a few hundred of [0, PK]
-				constexpr int PKI = ( IO == 4 ? 255 : 65535 );
-				const int q0 = min( max( (int) ( v.x + 0.5f ), 0 ), PKI );
-				const int q1 = min( max( (int) ( v.y + 0.5f ), 0 ), PKI );
-
-				if constexpr( IO == 4 )
-				{
-					__builtin_amdgcn_raw_buffer_store_b8( (unsigned char) q0, rs,
-						dlv, soff, U2_STAUX );
-					__builtin_amdgcn_raw_buffer_store_b8( (unsigned char) q1, rs,
-						dlv2, soff, U2_STAUX );
-				}
-				else
-				{
-					__builtin_amdgcn_raw_buffer_store_b16( (unsigned short) q0, rs,
-						dlv, soff, U2_STAUX );
-					__builtin_amdgcn_raw_buffer_store_b16( (unsigned short) q1, rs,
-						dlv2, soff, U2_STAUX );
-				}
-			}
-			else
-			{
-				constexpr float PK = ( IO == 1 ? 255.0f : 65535.0f );
-				float t0 = (float) (int) ( v.x + 0.5f );
-				float t1 = (float) (int) ( v.y + 0.5f );
-				t0 = fminf( fmaxf( t0, 0.0f ), PK );
-				t1 = fminf( fmaxf( t1, 0.0f ), PK );
-				t0 = avirhip_x86_round_fix( v.x, t0, PK );
-				t1 = avirhip_x86_round_fix( v.y, t1, PK );
-
-				if constexpr( IO == 1 )
-				{
-					__builtin_amdgcn_raw_buffer_store_b8(
-						(unsigned char) (unsigned) t0, rs, dlv, soff, U2_STAUX );
-					__builtin_amdgcn_raw_buffer_store_b8(
-						(unsigned char) (unsigned) t1, rs, dlv2, soff, U2_STAUX );
-				}
-				else
-				{
-					__builtin_amdgcn_raw_buffer_store_b16(
-						(unsigned short) (unsigned) t0, rs, dlv, soff, U2_STAUX );
-					__builtin_amdgcn_raw_buffer_store_b16(
-						(unsigned short) (unsigned) t1, rs, dlv2, soff, U2_STAUX );
-				}
-			}
-		};
+		// (the caller's pixels, IO != 0: `store_io`, `store_g`)
+#include "up2_store.inl"
 
 		// (a row's products and the sums they go to, by MODE: `vinterp`)
 #include "up2_vt.inl"
@@ -1328,6 +1284,20 @@ __attribute__(( amdgpu_waves_per_eu( 4, 4 ))) k_up2( const Up2Params P )
 						// accumulation chains into them): an unwanted row goes
 						// through a zero-length view of the destination, whose
 						// range check drops the store.
+						if constexpr( GOUT )
+						{
+							const __amdgpu_buffer_rsrc_t r1 =
+								__builtin_amdgcn_make_buffer_rsrc( dbase, 0,
+								( rmask & ( 1u << ( 2 * rr )) ? 0x7fffffff : 0 ),
+								0x00020000 );
+							const __amdgpu_buffer_rsrc_t r2 =
+								__builtin_amdgcn_make_buffer_rsrc( dbase, 0,
+								( rmask & ( 2u << ( 2 * rr )) ? 0x7fffffff : 0 ),
+								0x00020000 );
+
+							store_g( od, ed, est, r1, r2, so );
+						}
+						else
 						if constexpr( IO != 0 )
 						{
 							store_io( od, __builtin_amdgcn_make_buffer_rsrc(
@@ -1582,6 +1552,7 @@ struct Up2Data
 	float* d_coef;
 	bool vsym; // vertical bank phase bit-symmetric: fo[t] == fe[11-t]
 	bool hsym; // ... and the horizontal one
+	bool gain16; // samples within [-1, 1] give sums within [-16, 16] (IO 9)
 };
 
 // Whether the plan runs the transposed form k_up2< true, ... >: both axes'
@@ -1648,6 +1619,8 @@ int up2_prepare( avirhip_plan* p )
 				sizeof( float )) == 0 );
 		}
 
+		D -> gain16 = ( up2_axis_gain( D -> h.f, D -> h.fe, D -> h.fo ) *
+			up2_axis_gain( D -> v.f, D -> v.fe, D -> v.fo ) <= 15.0 );
 		p -> up2 = D;
 		p -> fused_ok |= 4;
 		p -> auto_path = 4;
@@ -1666,16 +1639,43 @@ void up2_release( avirhip_plan* p )
 	p -> up2 = nullptr;
 }
 
+// The gamma plan whose uint8 result the kernel de-linearises and stores itself:
+// the thresholds of the output stage exist, the float pipeline
+static bool up2_gamma_u8( const avirhip_plan* p )
+{
+	return( p -> gamma && p -> out_type == AVIRHIP_U8 &&
+		p -> d_gthr != nullptr && !p -> fp4 && !p -> f64 );
+}
+
+// up2_run's `io` of a gamma plan (any other keeps its own): 8, or 9 behind a
+// uint8 / uint16 source when `gain16` (up2_params.h); 0: none the kernel stores
+static int up2_gamma_io( const avirhip_plan* p, const int io, const bool gain16 )
+{
+	if( !p -> gamma )
+	{
+		return( io );
+	}
+
+	return( !up2_gamma_u8( p ) ? 0 : ( gain16 && ( p -> in_type == AVIRHIP_U8 ||
+		p -> in_type == AVIRHIP_U16 ) ? 9 : 8 ));
+}
+
 // Whether the plan's marching kernel can store the caller's pixels itself
-// (up2_run's `iout`): the transposed vertical phase, default ditherer, no
-// gamma, and uint8 / uint16 without bit-depth truncation, float pixels of
+// (up2_run's `iout`): the transposed vertical phase, default ditherer, and
+// without gamma uint8 / uint16 without bit-depth truncation, float pixels of
 // 1-3 channels or half / bfloat16 RGBA pixels (such pixels of 1-3 channels
-// leave through the output stage).
+// leave through the output stage); with gamma uint8 pixels (up2_gamma_u8).
 bool up2_stores_io( const avirhip_plan* p )
 {
 	const Up2Data* D = (const Up2Data*) p -> up2;
 
-	return( up2_vt( p, D ) && !p -> gamma &&
+	if( p -> gamma )
+	{
+		return( up2_vt( p, D ) && p -> dither == AVIRHIP_DITHER_DEF &&
+			up2_gamma_u8( p ));
+	}
+
+	return( up2_vt( p, D ) &&
 		p -> dither == AVIRHIP_DITHER_DEF &&
 		(( p -> out_type == AVIRHIP_U8 && p -> tr_mul == 1.0 &&
 		p -> pk_out == 255.0 ) ||
@@ -1730,7 +1730,9 @@ int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 			( p -> out_type == AVIRHIP_BF16 && p -> io_ch == 4 &&
 			( (uintptr_t) iout & 3 ) == 0 ? 7 : 0 )))));
 
-		if( !vt || io == 0 || p -> dither != AVIRHIP_DITHER_DEF || p -> gamma )
+		// (a gamma plan: 8 / 9, the de-linearised uint8 result, or none)
+		if( !vt || ( io = up2_gamma_io( p, io, D -> gain16 )) == 0 ||
+			p -> dither != AVIRHIP_DITHER_DEF )
 		{
 			return( 1 );
 		}
@@ -1742,7 +1744,6 @@ int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 		{
 			io += 3;
 		}
-
 	}
 
 	// the integer image as it lies (k_up2< true, IO, SRC >): results of
@@ -1761,8 +1762,7 @@ int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 		const long sb = raw_stride * esz;
 
 		if(( f16kind ? io != 5 + f16kind || p -> io_ch != 4 :
-			( io != 4 && io != 5 ) ||
-			( p -> in_type != AVIRHIP_U8 && p -> in_type != AVIRHIP_U16 )) ||
+			!up2_int_raw_ok( p, io )) || // (io 4 / 5; a gamma plan: 9, uint8)
 			( p -> io_ch != 3 && p -> io_ch != 4 ) ||
 			win.rows > 0 || ( (uintptr_t) raw & ( esz - 1 )) ||
 			( esz == 2 && p -> io_ch == 4 && (( (uintptr_t) raw | sb ) & 3 )) ||
@@ -1771,7 +1771,7 @@ int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 			return( 1 );
 		}
 
-		srck = f16kind * 100 + esz * 10 + p -> io_ch;
+		srck = ( p -> gamma ? 300 : f16kind * 100 ) + esz * 10 + p -> io_ch;
 		src = (const float*) raw;
 		src_stride = sb;
 	}
@@ -1805,7 +1805,7 @@ int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 	P.srow_lo = row0; P.srow_hi = row1;
 	P.nstrips = ( p -> new_w + U2_TW - 1 ) / U2_TW;
 	P.ibase = iout; P.ich = p -> io_ch;
-	P.istride_b = p -> new_w * p -> io_ch * ( io == 1 || io == 4 ? 1 :
+	P.istride_b = p -> new_w * p -> io_ch * ( io == 1 || io == 4 || io >= 8 ? 1 :
 		( io == 2 || io == 5 || io == 6 || io == 7 ? 2 : 4 ));
 
 	// Chunk heights (up2_chunks.h). A chunk of h source rows costs
@@ -1873,6 +1873,28 @@ int up2_run( avirhip_plan* p, const float* src, long src_stride, float* dst,
 
 	const char* pad = getenv( "AVIRHIP_UP2_LDSPAD" ); // residency experiments
 	const int ldspad = ( pad != nullptr ? atoi( pad ) : 0 );
+	if( io >= 8 )
+	{
+		Up2GParams PG;
+		(Up2Params&) PG = P;
+		up2_gamma_params( p, PG.G );
+#if U2_RB == 8 // (up2_vt: no other build comes here)
+#define U2_GAMMA( IOK, SK ) hipLaunchKernelGGL(( k_up2< true, IOK, SK > ), \
+	dim3( items ), dim3( U2_NT ), ldspad, st, PG )
+		switch( srck )
+		{
+			case 313: U2_GAMMA( 9, 313 ); break;
+			case 314: U2_GAMMA( 9, 314 ); break;
+			default:
+				if( io == 9 ) U2_GAMMA( 9, 0 );
+				else U2_GAMMA( 8, 0 );
+		}
+#undef U2_GAMMA
+#else
+		return( 1 );
+#endif
+	}
+	else
 	if( srck != 0 )
 	{
 #define U2_RAW( IOK, SK ) hipLaunchKernelGGL(( k_up2< U2_RB == 8, \

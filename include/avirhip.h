@@ -362,6 +362,12 @@ int avirhip_plan_get_path(const avirhip_plan* plan);
  * writes a float result for the output stage, where it would read or store the
  * caller's integer / half / bfloat16 pixels itself (the A/B and differential form of the
  * fused I/O; float RGBA images are the kernel's own format either way).
+ * With UseSRGBGamma and a uint8 result: the gamma pack pass, the float kernel
+ * and the de-linearising output stage, where the kernel would linearise a
+ * uint8 RGB / RGBA source and de-linearise and store the result itself (frames
+ * of AVIRHIP_UP2SRGB_RAW_MINPIX to AVIRHIP_UP2SRGB_RAW_MAXPIX source pixels,
+ * 1,700,000 to 2,700,000 unless set; the store alone up to
+ * AVIRHIP_UP2SRGB_STORE_MAXPIX, 0 unless set: environment, read per call).
  * On a CLancIR plan: the pack pass and the output stage always run, whatever
  * the path -- no kernel reads the caller's image as it lies and none stores the
  * caller's pixels itself (AVIRHIP_NO_FUSED_OUT for this plan alone) */

@@ -68,8 +68,24 @@ stage: the road before, the yardstick), alternating: RGBA uint8 -> uint8, RGBA
 uint8 -> float32, RGB uint8 -> uint8 (the store side only), and the RGBA uint8
 call without gamma for scale.
 
+--up2srgb measures exact-2x upsizing of 8-bit images with sRGB gamma
+(CImageResizer(8), UseSRGBGamma, AlphaIndex 3 for RGBA) on path 4 by the same
+method -- 1920x1080 -> 3840x2160 and 3840x2160 -> 7680x4320 -- RGBA and RGB
+uint8 -> uint8 as they run (k_up2's SRC 313 / 314 and IO 9 kinds), under
+AVIRHIP_VARIANT_UP2_UNFUSED_IO (pack pass, k_up2, output stage: the road
+before, with PARENT.so also on that build) and without gamma (k_up2< true, 4,
+13 / 14 >); float32 -> uint8 RGBA and RGB with gamma, the store side alone
+(IO 8 behind the pack pass) against the road before; the residency of the
+gamma kinds under AVIRHIP_UP2_LDSPAD (1 KB on the store kind: seven -> six
+workgroups a CU; 4 KB on the raw kind: six -> five) and, with THR1K.so (`make
+thr1k`: the colour thresholds alone in LDS, alpha by its direct expression),
+of that form (raw kinds: seven workgroups; store kinds: eight); and float32 ->
+float32 RGBA in this library, with PARENT.so beside the parent's.
+
 usage: python tools/half_timing.py [--bf16 | --lancir | --dnf | --dnsrgb |
-       --gpass | --lancgp | --sacc] [PARENT.so] [REPS=5] [ONLY]
+       --up2srgb | --gpass | --lancgp | --sacc] [PARENT.so] [REPS=5] [ONLY]
+(--up2srgb: [PARENT.so] [REPS=5] [THR1K.so] [bounds]; `bounds`: the fused roads
+against the road before at six frame sizes from 640x360 to 3840x2160)
 (ONLY, with --gpass, --lancgp and --sacc: the shapes whose names hold one of
 these comma-separated words, e.g. "u8")"""
 import ctypes as C
@@ -424,6 +440,145 @@ def dnsrgb_main(argv):
         print("  %dx%d -> %dx%d (%d source pixels): %s" % (
             sw, sh, nw, nh, sw * sh, ", ".join(out)), flush=True)
         del keep, run, ring
+        torch.cuda.empty_cache()
+
+
+def up2srgb_main(argv):
+    """--up2srgb: the rows of the module docstring, CImageResizer(8) plans on
+    path 4; every row of a shape in one rotation."""
+    import numpy as np
+    import torch
+    import avir_amd
+    from avir_amd import abi, synth
+    parent = argv[1] if len(argv) > 1 and argv[1] != "-" else None
+    reps = int(argv[2]) if len(argv) > 2 else 5
+    lib = abi.load()
+    plib = abi.load_path(parent) if parent else None
+    alib = abi.load_path(argv[3]) if len(argv) > 3 else None
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    header(lib, parent)
+    TD = {abi.F32: torch.float32, abi.U8: torch.uint8}
+    ES = {abi.F32: 4, abi.U8: 1}
+    U = abi.VARIANT_UP2_UNFUSED_IO
+    g4 = avir_amd.CImageResizerVars()
+    g4.UseSRGBGamma, g4.AlphaIndex = 1, 3
+    g3 = avir_amd.CImageResizerVars()
+    g3.UseSRGBGamma = 1
+    # the kernel's gamma kinds whatever the frame size (the library routes by
+    # up2srgb_raw_minpix / _maxpix and up2srgb_store_maxpix, read per call)
+    F = {"AVIRHIP_UP2SRGB_RAW_MINPIX": "0",
+         "AVIRHIP_UP2SRGB_RAW_MAXPIX": "1000000000",
+         "AVIRHIP_UP2SRGB_STORE_MAXPIX": "1000000000"}
+    # BOUNDS: the fused roads against the road before over a ladder of frame
+    # sizes, which is where those two bounds come from
+    bounds = len(argv) > 4 and argv[4] == "bounds"
+    shapes = (("1080p", (1920, 1080)), ("2160p", (3840, 2160)))
+    if bounds:
+        shapes = tuple(("%dx%d" % g, g) for g in (
+            (640, 360), (1280, 720), (1920, 1080), (2560, 1440),
+            (3200, 1800), (3840, 2160)))
+    for name, (sw, sh) in shapes:
+        nw, nh = 2 * sw, 2 * sh
+        # (tag, library, channels, in, out, variant, vars, environment)
+        rows = []
+        for ch, gv in ((4, g4), (3, g3)):
+            c = "RGBA" if ch == 4 else "RGB"
+            rows += [("%s u8->u8 gamma, one launch" % c, lib, ch, abi.U8,
+                      abi.U8, 0, gv, F),
+                     ("%s u8->u8 gamma, pack + k_up2 + output stage" % c, lib,
+                      ch, abi.U8, abi.U8, U, gv, {})]
+            if bounds:
+                continue
+            if plib is not None:
+                rows.append(("%s u8->u8 gamma, parent build" % c, plib, ch,
+                             abi.U8, abi.U8, 0, gv, {}))
+            rows.append(("%s u8->u8 no gamma" % c, lib, ch, abi.U8, abi.U8, 0,
+                         None, {}))
+        for ch, gv in ((4, g4), (3, g3)):
+            c = "RGBA" if ch == 4 else "RGB"
+            rows += [("%s f32->u8 gamma, pack + k_up2 store" % c, lib, ch,
+                      abi.F32, abi.U8, 0, gv, F),
+                     ("%s f32->u8 gamma, pack + k_up2 + output stage" % c,
+                      lib, ch, abi.F32, abi.U8, U, gv, {})]
+        if not bounds:
+            rows += [("RGBA f32->u8 gamma, store, LDS + 1 KB (6 workgroups)",
+                      lib, 4, abi.F32, abi.U8, 0, g4,
+                      dict(F, AVIRHIP_UP2_LDSPAD="1024")),
+                     ("RGBA u8->u8 gamma, one launch, LDS + 4 KB "
+                      "(5 workgroups)", lib, 4, abi.U8, abi.U8, 0, g4,
+                      dict(F, AVIRHIP_UP2_LDSPAD="4096")),
+                     ("RGBA f32->f32", lib, 4, abi.F32, abi.F32, 0, None, {})]
+        if alib is not None and not bounds:
+            rows += [("RGBA u8->u8 gamma, one launch, 1 KB thresholds "
+                      "(7 workgroups)", alib, 4, abi.U8, abi.U8, 0, g4, F),
+                     ("RGB u8->u8 gamma, one launch, 1 KB thresholds "
+                      "(7 workgroups)", alib, 3, abi.U8, abi.U8, 0, g3, F),
+                     ("RGBA f32->u8 gamma, store, 1 KB thresholds "
+                      "(8 workgroups)", alib, 4, abi.F32, abi.U8, 0, g4, F)]
+        if plib is not None and not bounds:
+            rows.append(("RGBA f32->f32, parent build", plib, 4, abi.F32,
+                         abi.F32, 0, None, {}))
+        pairs = [(rows[i][0], rows[i + 1][0]) for i in range(len(rows) - 1)
+                 if "one launch" in rows[i][0] or "k_up2 store" in rows[i][0]]
+        pairs = [(x, y) for x, y in pairs if "output stage" in y]
+        run, keep, first = {}, [], {}
+        for tag, L, ch, ti, to, variant, vars_, env in rows:
+            base = synth.lcg_u8((sh, sw, ch))
+            if ti == abi.F32:
+                base = (base.astype(np.float32) / np.float32(255.0))
+            pair = sw * sh * ch * ES[ti] + nw * nh * ch * ES[to]
+            n = max(2, -(-(512 << 20) // pair))
+            ring = []
+            for i in range(n):
+                s = torch.from_numpy(np.roll(base, i, axis=0)).to(dev)
+                d = torch.empty((nh, nw, ch), dtype=TD[to], device=dev)
+                ring.append((s, d))
+            with abi.using(L):
+                r = avir_amd.CImageResizer(8 if to == abi.U8 else 16)
+                p = r.plan(sw, sh, nw, nh, ch, 0.0, vars_, ti, to)
+            abi.check(L.avirhip_plan_set_path(p, abi.PATH_UP2), "path 4")
+            abi.check(L.avirhip_plan_set_variant(p, variant), "variant")
+            keep.append((r, ring))
+
+            def once(L=L, p=p, ring=ring, env=env):
+                t = 0.0
+                ms = C.c_double()
+                with _env(env):
+                    for s, d in ring:
+                        abi.check(L.avirhip_time_resize(
+                            p, s.data_ptr(), d.data_ptr(), 1, st,
+                            C.byref(ms)), "time_resize")
+                        t += ms.value
+                return t / len(ring)
+            run[tag] = (once, pair, n, p, L)
+            first[tag] = ring[0][1]
+        for tag in run:  # warm-up, clocks
+            for _ in range(10):
+                run[tag][0]()
+        torch.cuda.synchronize()
+        same = [torch.equal(first[x], first[y]) for x, y in pairs]
+        res = {tag: [] for tag in run}
+        loops = 10 if sw * sh > 4000000 else 20
+        for _ in range(reps):
+            for tag in run:
+                res[tag].append(
+                    sum(run[tag][0]() for _ in range(loops)) / loops)
+        print("%s (%dx%d -> %dx%d, path 4), %d reps x %d ring passes:" % (
+            name, sw, sh, nw, nh, reps, loops))
+        for tag in run:
+            v = sorted(res[tag])
+            med = v[len(v) // 2]
+            print("  %-58s %.4f ms  (min %.4f max %.4f)  %6.1f MB/call  "
+                  "%.2f TB/s  ring %d  plan holds %.1f MB" % (
+                      tag, med, v[0], v[-1], run[tag][1] / 1e6,
+                      run[tag][1] / med / 1e9, run[tag][2],
+                      run[tag][4].avirhip_plan_device_bytes(run[tag][3]) /
+                      1e6), flush=True)
+        for (x, y), ok in zip(pairs, same):
+            print("  (%s) and (%s) bit-identical: %s" % (x, y, ok),
+                  flush=True)
+        del keep, run, first
         torch.cuda.empty_cache()
 
 
@@ -867,6 +1022,8 @@ def main():
         return dnf_main([a for a in sys.argv if a != "--dnf"])
     if "--dnsrgb" in sys.argv:
         return dnsrgb_main([a for a in sys.argv if a != "--dnsrgb"])
+    if "--up2srgb" in sys.argv:
+        return up2srgb_main([a for a in sys.argv if a != "--up2srgb"])
     import numpy as np
     import torch
     import avir_amd
