@@ -289,3 +289,62 @@ class CLancIR(object):
         if rc != NewHeight:
             raise AvirHipError("CLancIR.resizeImage returned %d" % rc)
         return dst
+
+    # Planes (an extension: the reference has no such call).
+    def resizePlanes(self, SrcBuf, SrcWidth, SrcHeight, NewBuf, NewWidth,
+                     NewHeight, PlaneCount, SrcPlaneSize=0, NewPlaneSize=0,
+                     aParams=None):
+        """`PlaneCount` single-channel planes of one geometry -- a
+        channel-first image, a batch -- in one call
+        (avirhip_lancir_resize_planes): plane i of the result is, bit for
+        bit, resizeImage(..., ElCount=1) of plane i of the source. Planes lie
+        `SrcPlaneSize` / `NewPlaneSize` elements apart (0: tightly packed);
+        rows at aParams.SrcSSize / NewSSize. Returns NewHeight, or 0 on a
+        parameter error."""
+        if SrcBuf is None or NewBuf is None:
+            return 0
+        sp, sm, st, s1 = _buf(SrcBuf)
+        dp, dm, dt, s2 = _buf(NewBuf)
+        if (min(SrcWidth, SrcHeight, NewWidth, NewHeight, PlaneCount) > 0
+                and sp != dp):
+            ss = aParams.SrcSSize if aParams is not None else 0
+            ns = aParams.NewSSize if aParams is not None else 0
+            ss = ss if ss >= 1 else SrcWidth
+            ns = ns if ns >= 1 else NewWidth
+            sps = SrcPlaneSize if SrcPlaneSize != 0 else SrcHeight * ss
+            nps = NewPlaneSize if NewPlaneSize != 0 else NewHeight * ns
+            _need(SrcBuf, (PlaneCount - 1) * sps + (SrcHeight - 1) * ss
+                  + SrcWidth, "SrcBuf")
+            _need(NewBuf, (PlaneCount - 1) * nps + (NewHeight - 1) * ns
+                  + NewWidth, "NewBuf")
+        with _on_device_of(SrcBuf, NewBuf):
+            rc = self._lib.avirhip_lancir_resize_planes(
+                self._h, sp, sm, SrcWidth, SrcHeight, dp, dm, NewWidth,
+                NewHeight, PlaneCount, SrcPlaneSize, NewPlaneSize,
+                C.byref(aParams) if aParams is not None else None, st, dt,
+                s1 or s2)
+        return abi.check(rc, "avirhip_lancir_resize_planes")
+
+    def resize_planes(self, src, NewWidth, NewHeight, out_dtype=None,
+                      aParams=None):
+        """src: a contiguous (..., H, W) array/tensor -> new (..., NewHeight,
+        NewWidth); all leading dimensions fold into the plane count."""
+        if len(src.shape) < 2:
+            raise ValueError("resize_planes: (..., H, W) expected")
+        lead = tuple(int(n) for n in src.shape[:-2])
+        h, w = int(src.shape[-2]), int(src.shape[-1])
+        n = 1
+        for d in lead:
+            n *= d
+        shape = lead + (NewHeight, NewWidth)
+        if _is_torch(src):
+            import torch
+            dst = torch.empty(shape, device=src.device,
+                              dtype=out_dtype or src.dtype)
+        else:
+            dst = np.empty(shape, out_dtype or src.dtype)
+        rc = self.resizePlanes(src, w, h, dst, NewWidth, NewHeight, n, 0, 0,
+                               aParams)
+        if rc != NewHeight:
+            raise AvirHipError("CLancIR.resizePlanes returned %d" % rc)
+        return dst

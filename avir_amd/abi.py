@@ -202,6 +202,12 @@ PROTOTYPES = {
     "avirhip_lancir_get_plan": (_I, [_VP, _I, _I, _I, _I, _I,
                                      C.POINTER(LancirParams), _I, _I,
                                      C.POINTER(_VP)]),
+    "avirhip_resize_planes": (_I, [_VP, _VP, _I, C.c_longlong, _VP, _I,
+                                   C.c_longlong, _I, _VP]),
+    "avirhip_lancir_resize_planes": (_I, [_VP, _VP, _I, _I, _I, _VP, _I, _I,
+                                          _I, _I, C.c_longlong, C.c_longlong,
+                                          C.POINTER(LancirParams), _I, _I,
+                                          _VP]),
 }
 
 _lib = None

@@ -1008,3 +1008,293 @@ try
 AVIRHIP_CATCH( avirhip_lancir_resize )
 
 } // extern "C"
+
+// ---------------------------------------------------------------------
+// Planar calls (include/avirhip.h, avirhip_resize_planes): n single-channel
+// planes of one geometry at a plane stride -- a channel-first image, a batch.
+// ---------------------------------------------------------------------
+
+namespace {
+
+// One side of a planar call, in elements: row pitch, plane stride (0 = tightly
+// packed), and the bytes from the first plane's first element to the last
+// plane's last one.
+struct PlanesSide
+{
+	long pitch, stride;
+	size_t es, row_bytes, span_bytes;
+};
+
+// Host arithmetic only (no device): the stride rule of the contract.
+int planes_side( const char* what, int w, int h, long pitch, long long stride,
+	int n_planes, int type, PlanesSide& S )
+{
+	S.pitch = ( pitch < 1 ? (long) w : pitch );
+	S.es = dtype_size( type );
+	S.row_bytes = (size_t) w * S.es;
+	const long need = (long) ( h - 1 ) * S.pitch + w;
+
+	if( S.pitch < w )
+	{
+		set_error( "planes: %s row pitch %ld is shorter than a row of %d", what,
+			S.pitch, w );
+		return( AVIRHIP_EINVAL );
+	}
+
+	S.stride = ( stride == 0 ? (long) h * S.pitch : (long) stride );
+
+	if( stride < 0 || S.stride < need )
+	{
+		set_error( "planes: %s plane stride %lld is shorter than a plane "
+			"(%ld elements)", what, stride, need );
+		return( AVIRHIP_EINVAL );
+	}
+
+	size_t gap = 0;
+
+	if( !mul_fits( (size_t) ( n_planes - 1 ), (size_t) S.stride, S.es, 1, &gap ) ||
+		gap + (size_t) need * S.es < gap )
+	{
+		set_error( "planes: %s planes exceed the address space", what );
+		return( AVIRHIP_EINVAL );
+	}
+
+	S.span_bytes = gap + (size_t) need * S.es;
+	return( AVIRHIP_OK );
+}
+
+bool planes_share( const void* a, size_t na, const void* b, size_t nb )
+{
+	return( (const char*) a < (const char*) b + nb &&
+		(const char*) b < (const char*) a + na );
+}
+
+// a per-call device allocation (host buffers are staged: not a hot path)
+struct DevBuf
+{
+	void* p;
+	DevBuf() : p( nullptr ) {}
+	~DevBuf() { if( p != nullptr ) (void) hipFree( p ); }
+};
+
+struct CurDevice
+{
+	int keep;
+	bool on;
+	explicit CurDevice( int want ) : keep( 0 ), on( false )
+	{
+		if( hipGetDevice( &keep ) == hipSuccess && keep != want )
+		{
+			on = ( hipSetDevice( want ) == hipSuccess );
+		}
+	}
+	~CurDevice() { if( on ) (void) hipSetDevice( keep ); }
+};
+
+} // namespace
+
+extern "C" {
+
+int avirhip_resize_planes( avirhip_plan* p, const void* src, int src_mem,
+	long long src_plane_stride, void* dst, int dst_mem,
+	long long dst_plane_stride, int n_planes, void* stream )
+try
+{
+	avirhip::clear_error();
+	if( p == nullptr || src == nullptr || dst == nullptr )
+	{
+		set_error( "resize_planes: null argument" );
+		return( AVIRHIP_EINVAL );
+	}
+
+	if( !p -> is_lancir || p -> io_ch != 1 )
+	{
+		set_error( "resize_planes: a CLancIR plan of one channel is required "
+			"(this one: %s, %d channels)", p -> is_lancir ? "CLancIR" :
+			"CImageResizer", p -> io_ch );
+		return( AVIRHIP_EUNSUPPORTED );
+	}
+
+	if( n_planes < 1 )
+	{
+		set_error( "resize_planes: n_planes %d", n_planes );
+		return( AVIRHIP_EINVAL );
+	}
+
+	PlanesSide S, D;
+	int rc = planes_side( "source", p -> src_w, p -> src_h, p -> src_stride,
+		src_plane_stride, n_planes, p -> in_type, S );
+	if( rc == 0 ) rc = planes_side( "result", p -> new_w, p -> new_h,
+		p -> new_stride, dst_plane_stride, n_planes, p -> out_type, D );
+
+	if( rc != 0 )
+	{
+		return( rc );
+	}
+
+	if( planes_share( src, S.span_bytes, dst, D.span_bytes ))
+	{
+		set_error( "resize_planes: source and result planes share bytes" );
+		return( AVIRHIP_EINVAL );
+	}
+
+	src_mem = avirhip_resolve_mem( src, src_mem );
+	dst_mem = avirhip_resolve_mem( dst, dst_mem );
+	const bool host_src = ( src_mem == AVIRHIP_MEM_HOST );
+	const bool host_dst = ( dst_mem == AVIRHIP_MEM_HOST );
+	hipStream_t st = (hipStream_t) stream;
+	CurDevice dev( p -> device );
+	DevBuf bs, bd;
+	const char* dsrc = (const char*) src;
+	char* ddst = (char*) dst;
+	const size_t sps = (size_t) S.stride * S.es, spb = (size_t) S.pitch * S.es;
+	const size_t dps = (size_t) D.stride * D.es, dpb = (size_t) D.pitch * D.es;
+
+	// host buffers: staged in the caller's own layout, rows only
+	if( host_src )
+	{
+		AVIRHIP_HIPCHECK( hipMalloc( &bs.p, S.span_bytes ));
+		dsrc = (const char*) bs.p;
+
+		for( int i = 0; i < n_planes; i++ )
+		{
+			AVIRHIP_HIPCHECK( hipMemcpy2DAsync( (char*) bs.p + i * sps, spb,
+				(const char*) src + i * sps, spb, S.row_bytes, p -> src_h,
+				hipMemcpyHostToDevice, st ));
+		}
+	}
+
+	if( host_dst )
+	{
+		AVIRHIP_HIPCHECK( hipMalloc( &bd.p, D.span_bytes ));
+		ddst = (char*) bd.p;
+	}
+
+	const char* why = "";
+	rc = lancp_run( p, dsrc, ddst, S.stride, D.stride, n_planes, st, &why );
+
+	if( rc == 1 )
+	{
+		// the plan's own road, plane by plane (it serialises itself)
+		if( getenv( "AVIRHIP_VERBOSE" ) != nullptr )
+		{
+			fprintf( stderr, "planes: per-plane road (%s)\n", why );
+		}
+
+		rc = AVIRHIP_OK;
+
+		for( int i = 0; i < n_planes && rc == 0; i++ )
+		{
+			rc = avirhip_resize( p, dsrc + i * sps, AVIRHIP_MEM_DEVICE,
+				ddst + i * dps, AVIRHIP_MEM_DEVICE, stream );
+		}
+	}
+
+	if( rc == 0 && host_dst )
+	{
+		for( int i = 0; i < n_planes; i++ )
+		{
+			AVIRHIP_HIPCHECK( hipMemcpy2DAsync( (char*) dst + i * dps, dpb,
+				ddst + i * dps, dpb, D.row_bytes, p -> new_h,
+				hipMemcpyDeviceToHost, st ));
+		}
+	}
+
+	if( host_src || host_dst )
+	{
+		AVIRHIP_HIPCHECK( hipStreamSynchronize( st ));
+	}
+
+	return( rc );
+}
+AVIRHIP_CATCH( avirhip_resize_planes )
+
+int avirhip_lancir_resize_planes( avirhip_lancir* l, const void* src,
+	int src_mem, int src_w, int src_h, void* dst, int dst_mem, int new_w,
+	int new_h, int n_planes, long long src_plane_stride,
+	long long dst_plane_stride, const avirhip_lancir_params* params,
+	int in_type, int out_type, void* stream )
+try
+{
+	avirhip::clear_error();
+	// Parameter errors return 0, as avirhip_lancir_resize (lancir.h:392-407).
+	if( l == nullptr || src_w < 0 || src_h < 0 || new_w <= 0 || new_h <= 0 ||
+		src == nullptr || dst == nullptr || src == dst ||
+		( params != nullptr && params -> la < 2.0 ))
+	{
+		return( 0 );
+	}
+
+	if( n_planes < 1 || in_type < 0 || in_type > AVIRHIP_BF16 || out_type < 0 ||
+		out_type > AVIRHIP_BF16 )
+	{
+		set_error( "lancir_resize_planes: n_planes %d, element types %d, %d",
+			n_planes, in_type, out_type );
+		return( AVIRHIP_EINVAL );
+	}
+
+	// the stride rule and the overlap rule, before any plan exists
+	const bool empty = ( src_w == 0 || src_h == 0 );
+	PlanesSide S, D;
+	int rc = planes_side( "result", new_w, new_h,
+		params != nullptr ? params -> NewSSize : 0, dst_plane_stride, n_planes,
+		out_type, D );
+	if( rc == 0 && !empty ) rc = planes_side( "source", src_w, src_h,
+		params != nullptr ? params -> SrcSSize : 0, src_plane_stride, n_planes,
+		in_type, S );
+
+	if( rc != 0 )
+	{
+		return( rc );
+	}
+
+	if( !empty && planes_share( src, S.span_bytes, dst, D.span_bytes ))
+	{
+		set_error( "lancir_resize_planes: source and result planes share "
+			"bytes" );
+		return( AVIRHIP_EINVAL );
+	}
+
+	if( empty )
+	{
+		// Zero-filled rows honouring NewSSize, lancir.h:413-425, plane by plane.
+		dst_mem = avirhip_resolve_mem( dst, dst_mem );
+
+		for( int i = 0; i < n_planes; i++ )
+		{
+			char* const op = (char*) dst + (size_t) i * D.stride * D.es;
+
+			if( dst_mem == AVIRHIP_MEM_HOST )
+			{
+				for( int y = 0; y < new_h; y++ )
+				{
+					memset( op + (size_t) y * D.pitch * D.es, 0, D.row_bytes );
+				}
+			}
+			else
+			{
+				AVIRHIP_HIPCHECK( hipMemset2DAsync( op, (size_t) D.pitch * D.es,
+					0, D.row_bytes, new_h, (hipStream_t) stream ));
+			}
+		}
+
+		return( new_h );
+	}
+
+	avirhip_plan* p = nullptr;
+	rc = lancir_acquire( l, src_w, src_h, new_w, new_h, 1, params, in_type,
+		out_type, false, &p );
+
+	if( rc != 0 )
+	{
+		return( rc );
+	}
+
+	rc = avirhip_resize_planes( p, src, src_mem, src_plane_stride, dst,
+		dst_mem, dst_plane_stride, n_planes, stream );
+	lancir_release( l, p );
+	return( rc != 0 ? rc : new_h );
+}
+AVIRHIP_CATCH( avirhip_lancir_resize_planes )
+
+} // extern "C"

@@ -609,4 +609,14 @@ bool lanc2h_image_ok( const void* ptr, int type, long stride );
 int lanc2h_run( const avirhip_plan* q, const ImageRef& src,
 	const LancirOut& out, int row0, int row1, hipStream_t st );
 
+// lancp.hip: the planes of a CLancIR plan of one channel (avirhip_resize_planes)
+// in one launch, one float per lane: `n_planes` source planes `src_ps` elements
+// apart, their results `dst_ps` elements apart, rows at the plan's pitches,
+// device memory. 1: the call is not its own (an element type outside uint8,
+// uint16, float, half, bfloat16; a base that is no multiple of the element
+// size; a tile of intermediate rows that exceeds its LDS) and `*why` names
+// what it missed; the caller runs the plan's own road per plane.
+int lancp_run( const avirhip_plan* p, const void* src, void* dst, long src_ps,
+	long dst_ps, int n_planes, hipStream_t st, const char** why );
+
 } // namespace avirhip

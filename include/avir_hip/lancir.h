@@ -136,6 +136,49 @@ public:
 			NewHeight, ElCount, &Params ));
 	}
 
+	/* An EXTENSION the reference does not have: `PlaneCount` single-channel
+	 * planes of one geometry (a channel-first image, a batch) in one call.
+	 * Plane i of the result is, bit for bit, resizeImage( ..., ElCount = 1 )
+	 * of plane i of the source. Planes lie SrcPlaneSize / NewPlaneSize
+	 * elements apart (0: tightly packed); rows at aParams' SrcSSize /
+	 * NewSSize. The contract: avirhip_resize_planes of avirhip.h. */
+	template< typename Tin, typename Tout >
+	int resizeImagePlanes( const Tin* const SrcBuf, const int SrcWidth,
+		const int SrcHeight, Tout* const NewBuf, const int NewWidth,
+		const int NewHeight, const int PlaneCount,
+		const long long SrcPlaneSize = 0, const long long NewPlaneSize = 0,
+		const CLancIRParams* const aParams = nullptr )
+	{
+		avirhip_lancir_params p;
+		avirhip_lancir_params_default( &p );
+
+		if( aParams != nullptr )
+		{
+			p.SrcSSize = aParams -> SrcSSize; p.NewSSize = aParams -> NewSSize;
+			p.kx = aParams -> kx; p.ky = aParams -> ky;
+			p.ox = aParams -> ox; p.oy = aParams -> oy;
+			p.la = aParams -> la;
+		}
+
+		const int rc = avirhip_lancir_resize_planes( h, SrcBuf,
+			AVIRHIP_MEM_AUTO, SrcWidth, SrcHeight, NewBuf, AVIRHIP_MEM_AUTO,
+			NewWidth, NewHeight, PlaneCount, SrcPlaneSize, NewPlaneSize, &p,
+			dt< Tin > :: v, dt< Tout > :: v, nullptr );
+
+		if( rc == AVIRHIP_ENOMEM )
+		{
+			throw std::bad_alloc();
+		}
+
+		if( rc < 0 )
+		{
+			throw std::runtime_error( std::string(
+				"avir::CLancIR::resizeImagePlanes: " ) + avirhip_last_error() );
+		}
+
+		return( rc );
+	}
+
 private:
 	avirhip_lancir* h;
 };

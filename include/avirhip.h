@@ -644,6 +644,58 @@ int avirhip_lancir_get_plan(avirhip_lancir* l, int src_w, int src_h,
 	int new_w, int new_h, int el_count, const avirhip_lancir_params* params,
 	int in_type, int out_type, avirhip_plan** out);
 
+/* Planar calls: n single-channel planes of one geometry -- a channel-first
+ * image (C x H x W), a batch (N x C x H x W is N * C planes) -- resized by one
+ * call. An extension: the reference has no such call, but it defines what a
+ * plane is.
+ *   Planes.   The call resizes n_planes >= 1 planes (less: AVIRHIP_EINVAL).
+ *             Plane i of the source starts i * src_plane_stride elements behind
+ *             `src`, plane i of the result i * dst_plane_stride elements behind
+ *             `dst`.
+ *   Geometry. Every plane is a src_w x src_h image of ONE channel; its row
+ *             pitch is CLancIRParams::SrcSSize / NewSSize elements, or the
+ *             width where that is < 1. The planes share one geometry, one
+ *             parameter set, one element type per side -- one plan.
+ *   Strides.  A plane stride of 0 means tightly packed planes (height x row
+ *             pitch). Otherwise it must be at least (height - 1) x pitch +
+ *             width, else AVIRHIP_EINVAL. There is no limit of 4 planes.
+ *   Result.   Plane i equals, bit for bit, what avir::CLancIR::resizeImage with
+ *             ElCount = 1 stores for plane i of the source, for every element
+ *             type pair avirhip_lancir_resize takes with one channel. Half and
+ *             bfloat16 keep the rule of AVIRHIP_F16 / AVIRHIP_BF16: widened
+ *             exactly, the float32 result computed with the plan's gain,
+ *             narrowed to nearest even, no clamp.
+ *   Rounding. Integer results round by the element's position in its own
+ *             scanline of new_w elements: whole groups of four to nearest even
+ *             behind the two clamps, the 1-3 element tail by + 0.5 truncation.
+ *   Untouched bytes. Nothing outside a result plane's rows is written: not
+ *             between rows (NewSSize padding), not between planes, not behind
+ *             the last plane.
+ *   Parameter errors return what avirhip_lancir_resize returns for them (0:
+ *             lancir.h:392-407); src == dst is one of them. A zero-sized source
+ *             zero-fills every result plane row by row.
+ *   Overlap.  Source and result spans that share bytes: AVIRHIP_EINVAL.
+ *   Memory.   Device buffers run asynchronously on `stream`; host buffers are
+ *             accepted and staged with plain copies inside the call.
+ * uint8, uint16, float32, half and bfloat16 planes on either side, bases that
+ * are multiples of the element size, run in ONE launch of a kernel whose lane
+ * is one float of one plane (lancp.hip); float64 and uint32 planes, other
+ * bases and kernels too long for its tile run the plan's own road once per
+ * plane -- the same bits ("Planes").
+ *
+ * Plan level: `plan` is a CLancIR plan of one channel; any other plan returns
+ * AVIRHIP_EUNSUPPORTED. Returns AVIRHIP_OK or an error code. */
+int avirhip_resize_planes(avirhip_plan* plan, const void* src, int src_mem,
+	long long src_plane_stride, void* dst, int dst_mem,
+	long long dst_plane_stride, int n_planes, void* stream);
+
+/* Front end: CLancIR::resizeImage over n_planes planes. Returns new_h, 0 on a
+ * parameter error, < 0 on any other error. */
+int avirhip_lancir_resize_planes(avirhip_lancir* l, const void* src, int src_mem,
+	int src_w, int src_h, void* dst, int dst_mem, int new_w, int new_h,
+	int n_planes, long long src_plane_stride, long long dst_plane_stride,
+	const avirhip_lancir_params* params, int in_type, int out_type, void* stream);
+
 /* Test hook: the `nth` host allocation (operator new) the CALLING THREAD makes
  * inside the library from now on throws std::bad_alloc (1 = the next one;
  * 0 = off). tests/test_abi.py sweeps it over every allocation of the planning
