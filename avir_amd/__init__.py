@@ -207,6 +207,59 @@ class CImageResizer(object):
         self.resizeImage(src, w, h, 0, dst, NewWidth, NewHeight, ch, k, aVars)
         return dst
 
+    # Planes (an extension: the reference has no such call).
+    def resizePlanes(self, SrcBuf, SrcWidth, SrcHeight, SrcScanlineSize,
+                     NewBuf, NewWidth, NewHeight, PlaneCount, SrcPlaneSize=0,
+                     NewPlaneSize=0, k=0.0, aVars=None):
+        """`PlaneCount` single-channel planes of one geometry -- a
+        channel-first image, a batch -- in one call
+        (avirhip_resizer_resize_planes): plane i of the result is, bit for
+        bit, resizeImage(..., ElCountIO=1, k, aVars) of plane i of the source.
+        Planes lie `SrcPlaneSize` / `NewPlaneSize` elements apart (0: tightly
+        packed); source rows at SrcScanlineSize, result rows tight."""
+        sp, sm, st, s1 = _buf(SrcBuf)
+        dp, dm, dt, s2 = _buf(NewBuf)
+        if min(SrcWidth, SrcHeight, NewWidth, NewHeight, PlaneCount) > 0:
+            ss = SrcScanlineSize if SrcScanlineSize >= 1 else SrcWidth
+            sps = SrcPlaneSize if SrcPlaneSize != 0 else SrcHeight * ss
+            nps = NewPlaneSize if NewPlaneSize != 0 else NewHeight * NewWidth
+            _need(SrcBuf, (PlaneCount - 1) * sps + (SrcHeight - 1) * ss
+                  + SrcWidth, "SrcBuf")
+            _need(NewBuf, (PlaneCount - 1) * nps + NewHeight * NewWidth,
+                  "NewBuf")
+        elif min(NewWidth, NewHeight, PlaneCount) > 0:
+            nps = NewPlaneSize if NewPlaneSize != 0 else NewHeight * NewWidth
+            _need(NewBuf, (PlaneCount - 1) * nps + NewHeight * NewWidth,
+                  "NewBuf")
+        with _on_device_of(SrcBuf, NewBuf):
+            abi.check(self._lib.avirhip_resizer_resize_planes(
+                self._h, sp, sm, SrcWidth, SrcHeight, SrcScanlineSize, dp, dm,
+                NewWidth, NewHeight, PlaneCount, SrcPlaneSize, NewPlaneSize,
+                float(k), C.byref(aVars) if aVars is not None else None, st,
+                dt, s1 or s2), "avirhip_resizer_resize_planes")
+
+    def resize_planes(self, src, NewWidth, NewHeight, k=0.0, out_dtype=None,
+                      aVars=None):
+        """src: a contiguous (..., H, W) array/tensor -> new (..., NewHeight,
+        NewWidth); all leading dimensions fold into the plane count."""
+        if len(src.shape) < 2:
+            raise ValueError("resize_planes: (..., H, W) expected")
+        lead = tuple(int(n) for n in src.shape[:-2])
+        h, w = int(src.shape[-2]), int(src.shape[-1])
+        n = 1
+        for d in lead:
+            n *= d
+        shape = lead + (NewHeight, NewWidth)
+        if _is_torch(src):
+            import torch
+            dst = torch.empty(shape, device=src.device,
+                              dtype=out_dtype or src.dtype)
+        else:
+            dst = np.empty(shape, out_dtype or src.dtype)
+        self.resizePlanes(src, w, h, 0, dst, NewWidth, NewHeight, n, 0, 0, k,
+                          aVars)
+        return dst
+
 
 class CLancIRParams(abi.LancirParams):
     """avir::CLancIRParams (lancir.h:260-307)."""

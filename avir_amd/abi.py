@@ -208,6 +208,10 @@ PROTOTYPES = {
                                           _I, _I, C.c_longlong, C.c_longlong,
                                           C.POINTER(LancirParams), _I, _I,
                                           _VP]),
+    "avirhip_resizer_resize_planes": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _I,
+                                           _I, _I, _I, C.c_longlong,
+                                           C.c_longlong, C.c_double,
+                                           C.POINTER(Vars), _I, _I, _VP]),
 }
 
 _lib = None

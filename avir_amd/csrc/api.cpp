@@ -2537,6 +2537,7 @@ static avirhip_plan* new_plan()
 	avirhip_plan* p = new avirhip_plan();
 	p -> is_lancir = 0; p -> device = 0; p -> alloc_bytes = 0;
 	p -> path = 0; p -> variant = 0; p -> fused_ok = 0; p -> auto_path = 1; p -> fused = nullptr; p -> tile64 = nullptr; p -> up2 = nullptr; p -> lanc2 = nullptr; p -> gpass = nullptr;
+	p -> avirp.store( nullptr );
 	p -> packed = nullptr; p -> resbuf = nullptr; p -> lres = nullptr;
 	p -> stage_src = nullptr; p -> stage_dst = nullptr;
 	p -> stage_src_bytes = 0; p -> stage_dst_bytes = 0;
@@ -3367,6 +3368,7 @@ void avirhip_plan_destroy( avirhip_plan* p )
 	up2_release( p );
 	lanc2_release( p );
 	gpass_release( p );
+	avirp_release( p );
 
 	for( size_t i = 0; i < p -> allocs.size(); i++ )
 	{

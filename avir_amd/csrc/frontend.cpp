@@ -1107,10 +1107,10 @@ try
 		return( AVIRHIP_EINVAL );
 	}
 
-	if( !p -> is_lancir || p -> io_ch != 1 )
+	if( p -> io_ch != 1 )
 	{
-		set_error( "resize_planes: a CLancIR plan of one channel is required "
-			"(this one: %s, %d channels)", p -> is_lancir ? "CLancIR" :
+		set_error( "resize_planes: a plan of one channel is required (this "
+			"one: %s, %d channels)", p -> is_lancir ? "CLancIR" :
 			"CImageResizer", p -> io_ch );
 		return( AVIRHIP_EUNSUPPORTED );
 	}
@@ -1171,7 +1171,9 @@ try
 	}
 
 	const char* why = "";
-	rc = lancp_run( p, dsrc, ddst, S.stride, D.stride, n_planes, st, &why );
+	rc = ( p -> is_lancir ?
+		lancp_run( p, dsrc, ddst, S.stride, D.stride, n_planes, st, &why ) :
+		avirp_run( p, dsrc, ddst, S.stride, D.stride, n_planes, st, &why ));
 
 	if( rc == 1 )
 	{
@@ -1296,5 +1298,118 @@ try
 	return( rc != 0 ? rc : new_h );
 }
 AVIRHIP_CATCH( avirhip_lancir_resize_planes )
+
+int avirhip_resizer_resize_planes( avirhip_resizer* r, const void* src,
+	int src_mem, int src_w, int src_h, int src_scanline_size, void* dst,
+	int dst_mem, int new_w, int new_h, int n_planes,
+	long long src_plane_stride, long long dst_plane_stride, double k,
+	const avirhip_vars* vars, int in_type, int out_type, void* stream )
+try
+{
+	avirhip::clear_error();
+	if( r == nullptr || !avir_dtype_ok( out_type ))
+	{
+		set_error( "resize_planes: bad arguments" );
+		return( AVIRHIP_EINVAL );
+	}
+
+	if( n_planes < 1 )
+	{
+		set_error( "resizer_resize_planes: n_planes %d", n_planes );
+		return( AVIRHIP_EINVAL );
+	}
+
+	// (a geometry the reference refuses: its error comes from the planner, as
+	// avirhip_resizer_resize's does)
+	const bool sane = ( src_w >= 0 && src_h >= 0 && new_w >= 0 && new_h >= 0 &&
+		avir_dtype_ok( in_type ));
+	const bool empty = ( src_w == 0 || src_h == 0 );
+	PlanesSide S, D;
+
+	if( sane && ( empty || ( new_w > 0 && new_h > 0 )))
+	{
+		if( dst == nullptr || ( !empty && src == nullptr ))
+		{
+			set_error( "resizer_resize_planes: null image" );
+			return( AVIRHIP_EINVAL );
+		}
+
+		// the stride rule and the overlap rule, before any plan exists
+		int rc = ( new_w > 0 && new_h > 0 ? planes_side( "result", new_w, new_h,
+			0, dst_plane_stride, n_planes, out_type, D ) : AVIRHIP_OK );
+		if( rc == 0 && !empty ) rc = planes_side( "source", src_w, src_h,
+			src_scanline_size, src_plane_stride, n_planes, in_type, S );
+
+		if( rc != 0 )
+		{
+			return( rc );
+		}
+
+		if( !empty && planes_share( src, S.span_bytes, dst, D.span_bytes ))
+		{
+			set_error( "resizer_resize_planes: source and result planes share "
+				"bytes" );
+			return( AVIRHIP_EINVAL );
+		}
+	}
+
+	if( sane && empty )
+	{
+		// avir.h:4686-4697, plane by plane: rows of new_w elements, tight
+		if( new_w == 0 || new_h == 0 )
+		{
+			return( AVIRHIP_OK );
+		}
+
+		dst_mem = avirhip_resolve_mem( dst, dst_mem );
+
+		for( int i = 0; i < n_planes; i++ )
+		{
+			char* const op = (char*) dst + (size_t) i * D.stride * D.es;
+
+			if( dst_mem == AVIRHIP_MEM_HOST )
+			{
+				for( int y = 0; y < new_h; y++ )
+				{
+					memset( op + (size_t) y * D.pitch * D.es, 0, D.row_bytes );
+				}
+			}
+			else
+			{
+				AVIRHIP_HIPCHECK( hipMemset2DAsync( op, (size_t) D.pitch * D.es,
+					0, D.row_bytes, new_h, (hipStream_t) stream ));
+			}
+		}
+
+		return( AVIRHIP_OK );
+	}
+	else
+	if( sane && ( new_w == 0 || new_h == 0 ))
+	{
+		return( AVIRHIP_OK );
+	}
+
+	avirhip_plan* p = nullptr;
+	int rc = resizer_acquire( r, src_w, src_h, src_scanline_size, new_w,
+		new_h, 1, k, vars, in_type, out_type, false, &p );
+
+	if( rc != 0 )
+	{
+		return( rc );
+	}
+
+	if( !sane )
+	{
+		resizer_release( r, p );
+		set_error( "resizer_resize_planes: bad geometry" );
+		return( AVIRHIP_EINVAL );
+	}
+
+	rc = avirhip_resize_planes( p, src, src_mem, src_plane_stride, dst,
+		dst_mem, dst_plane_stride, n_planes, stream );
+	resizer_release( r, p );
+	return( rc );
+}
+AVIRHIP_CATCH( avirhip_resizer_resize_planes )
 
 } // extern "C"

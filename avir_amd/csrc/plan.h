@@ -207,8 +207,8 @@ struct avirhip_plan
 	void* stage_src; // host-pointer staging
 	void* stage_dst;
 	size_t stage_src_bytes, stage_dst_bytes;
+	std::atomic< void* > avirp; std::mutex avirp_mtx; // avirp.hip's lazy tile tables (see avirp_run)
 };
-
 
 namespace avirhip {
 
@@ -618,5 +618,15 @@ int lanc2h_run( const avirhip_plan* q, const ImageRef& src,
 // what it missed; the caller runs the plan's own road per plane.
 int lancp_run( const avirhip_plan* p, const void* src, void* dst, long src_ps,
 	long dst_ps, int n_planes, hipStream_t st, const char** why );
+
+// avirp.hip: the same for a CImageResizer plan of one channel -- k_avirp runs
+// the plan's lowered ops of both axes on LDS tiles, all planes in one launch.
+// 1: the call is not its own (float64 elements; gamma, error-diffusion,
+// fpclass_float4 and double plans; a base that is no multiple of the element
+// size; a chain of more than three ops; no tile within its LDS) and `*why`
+// names what it missed. avirp_release frees what the first call made.
+int avirp_run( avirhip_plan* p, const void* src, void* dst, long src_ps,
+	long dst_ps, int n_planes, hipStream_t st, const char** why );
+void avirp_release( avirhip_plan* p );
 
 } // namespace avirhip

@@ -293,6 +293,54 @@ public:
 		const double k, CImageResizerVars* const aVars = nullptr ) const
 	{
 		avirhip_vars v;
+		varsIn( aVars, ElCountIO, v );
+
+		hipdetail :: check( avirhip_resizer_resize( h, SrcBuf,
+			AVIRHIP_MEM_AUTO, SrcWidth, SrcHeight, SrcScanlineSize, NewBuf,
+			AVIRHIP_MEM_AUTO, NewWidth, NewHeight, ElCountIO, k, &v,
+			hipdetail :: dtype_of< Tin > :: v,
+			hipdetail :: dtype_of< Tout > :: v, nullptr ),
+			"avir::CImageResizer::resizeImage" );
+
+		varsOut< Tin, Tout >( aVars, v, SrcWidth, SrcHeight, SrcScanlineSize,
+			NewWidth, NewHeight, ElCountIO, k );
+	}
+
+	/* An extension (the reference has no such call): PlaneCount single-channel
+	 * planes of one geometry -- a channel-first image, a batch -- in one call
+	 * (avirhip_resizer_resize_planes, include/avirhip.h "CImageResizer
+	 * planes"). Plane i of the result is, bit for bit, resizeImage( ...,
+	 * ElCountIO = 1, k, aVars ) of plane i of the source; planes lie
+	 * SrcPlaneSize / NewPlaneSize elements apart (0: tightly packed), source
+	 * rows at SrcScanlineSize, result rows tight. Errors and *aVars as
+	 * resizeImage with ElCountIO = 1. */
+	template< typename Tin, typename Tout >
+	void resizeImagePlanes( const Tin* const SrcBuf, const int SrcWidth,
+		const int SrcHeight, int SrcScanlineSize, Tout* const NewBuf,
+		const int NewWidth, const int NewHeight, const int PlaneCount,
+		const long long SrcPlaneSize, const long long NewPlaneSize,
+		const double k, CImageResizerVars* const aVars = nullptr ) const
+	{
+		avirhip_vars v;
+		varsIn( aVars, 1, v );
+
+		hipdetail :: check( avirhip_resizer_resize_planes( h, SrcBuf,
+			AVIRHIP_MEM_AUTO, SrcWidth, SrcHeight, SrcScanlineSize, NewBuf,
+			AVIRHIP_MEM_AUTO, NewWidth, NewHeight, PlaneCount, SrcPlaneSize,
+			NewPlaneSize, k, &v, hipdetail :: dtype_of< Tin > :: v,
+			hipdetail :: dtype_of< Tout > :: v, nullptr ),
+			"avir::CImageResizer::resizeImagePlanes" );
+
+		varsOut< Tin, Tout >( aVars, v, SrcWidth, SrcHeight, SrcScanlineSize,
+			NewWidth, NewHeight, 1, k );
+	}
+
+private:
+	/* the caller-settable fields of *aVars for the C ABI, and the fpclass
+	 * fields the call writes into *aVars up front */
+	static void varsIn( CImageResizerVars* const aVars, const int ElCountIO,
+		avirhip_vars& v )
+	{
 		avirhip_vars_default( &v );
 
 		if( aVars != nullptr )
@@ -310,14 +358,14 @@ public:
 			aVars -> elalign = fpclass :: elalign;
 			aVars -> packmode = fpclass :: packmode;
 		}
+	}
 
-		hipdetail :: check( avirhip_resizer_resize( h, SrcBuf,
-			AVIRHIP_MEM_AUTO, SrcWidth, SrcHeight, SrcScanlineSize, NewBuf,
-			AVIRHIP_MEM_AUTO, NewWidth, NewHeight, ElCountIO, k, &v,
-			hipdetail :: dtype_of< Tin > :: v,
-			hipdetail :: dtype_of< Tout > :: v, nullptr ),
-			"avir::CImageResizer::resizeImage" );
-
+	template< typename Tin, typename Tout >
+	void varsOut( CImageResizerVars* const aVars, const avirhip_vars& v,
+		const int SrcWidth, const int SrcHeight, const int SrcScanlineSize,
+		const int NewWidth, const int NewHeight, const int ElCountIO,
+		const double k ) const
+	{
 		if( aVars != nullptr && SrcWidth > 0 && SrcHeight > 0 &&
 			NewWidth > 0 && NewHeight > 0 )
 		{
@@ -348,7 +396,6 @@ public:
 		}
 	}
 
-private:
 	avirhip_resizer* h;
 };
 

@@ -683,8 +683,31 @@ int avirhip_lancir_get_plan(avirhip_lancir* l, int src_w, int src_h,
  * bases and kernels too long for its tile run the plan's own road once per
  * plane -- the same bits ("Planes").
  *
- * Plan level: `plan` is a CLancIR plan of one channel; any other plan returns
- * AVIRHIP_EUNSUPPORTED. Returns AVIRHIP_OK or an error code. */
+ * CImageResizer planes. The same call for avir::CImageResizer, with the text
+ * above on planes, strides, overlap, memory and untouched bytes unchanged:
+ *   Geometry. Every plane is a src_w x src_h image of ONE channel. Source rows
+ *             lie SrcScanlineSize elements apart (the width where that is
+ *             < 1); result rows are new_w elements, tight: resizeImage has no
+ *             destination pitch.
+ *   Result.   Plane i equals, bit for bit, what
+ *             avir::CImageResizer< fpclass >::resizeImage with ElCountIO = 1
+ *             stores for plane i of the source: the same object (ResBitDepth,
+ *             SrcBitDepth, parameters, ditherer, fpclass), the same k, the same
+ *             aVars. AVIRHIP_F16 / AVIRHIP_BF16 keep their stated rule.
+ *             CImageResizerVarsBase is what the ElCountIO = 1 call writes.
+ *   Zero sizes. A zero-sized source zero-fills every result plane row by row;
+ *             a zero-sized destination is a no-op.
+ *   Parameter errors return what avirhip_resizer_resize returns for them.
+ * uint8, uint16, float32, half and bfloat16 planes, bases that are multiples of
+ * the element size, run in ONE launch of k_avirp (avirp.hip), which interprets
+ * the plan's lowered ops of both axes on LDS tiles; float64 planes, sRGB gamma,
+ * the error-diffusion ditherer, fpclass_float4 and fpclass_def<double>
+ * objects, other bases and filters too long for its tiles run the plan's own
+ * road once per plane -- the same bits ("CImageResizer planes").
+ *
+ * Plan level: `plan` is a CLancIR or a CImageResizer plan of one channel; any
+ * other channel count returns AVIRHIP_EUNSUPPORTED. Returns AVIRHIP_OK or an
+ * error code. */
 int avirhip_resize_planes(avirhip_plan* plan, const void* src, int src_mem,
 	long long src_plane_stride, void* dst, int dst_mem,
 	long long dst_plane_stride, int n_planes, void* stream);
@@ -695,6 +718,14 @@ int avirhip_lancir_resize_planes(avirhip_lancir* l, const void* src, int src_mem
 	int src_w, int src_h, void* dst, int dst_mem, int new_w, int new_h,
 	int n_planes, long long src_plane_stride, long long dst_plane_stride,
 	const avirhip_lancir_params* params, int in_type, int out_type, void* stream);
+
+/* Front end: CImageResizer::resizeImage with ElCountIO = 1 over n_planes
+ * planes. Returns what avirhip_resizer_resize returns. */
+int avirhip_resizer_resize_planes(avirhip_resizer* r, const void* src,
+	int src_mem, int src_w, int src_h, int src_scanline_size, void* dst,
+	int dst_mem, int new_w, int new_h, int n_planes,
+	long long src_plane_stride, long long dst_plane_stride, double k,
+	const avirhip_vars* vars, int in_type, int out_type, void* stream);
 
 /* Test hook: the `nth` host allocation (operator new) the CALLING THREAD makes
  * inside the library from now on throws std::bad_alloc (1 = the next one;
