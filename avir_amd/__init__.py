@@ -71,27 +71,156 @@ def _need(x, n, what):
                          % (what, _numel(x), n))
 
 
+def _torch_dtype_code(x):
+    import torch
+    tmap = {torch.uint8: U8, torch.float32: F32, torch.float64: F64,
+            torch.float16: F16, torch.bfloat16: BF16}
+    if hasattr(torch, "uint16"):
+        tmap[torch.uint16] = U16
+    if hasattr(torch, "uint32"):
+        tmap[torch.uint32] = U32
+    return tmap[x.dtype]
+
+
 def _buf(x):
     """-> (pointer, mem kind, dtype code, stream)"""
     if _is_torch(x):
         import torch
-        tmap = {torch.uint8: U8, torch.float32: F32, torch.float64: F64,
-                torch.float16: F16, torch.bfloat16: BF16}
-        if hasattr(torch, "uint16"):
-            tmap[torch.uint16] = U16
-        if hasattr(torch, "uint32"):
-            tmap[torch.uint32] = U32
         if not x.is_contiguous():
             raise ValueError("tensor must be contiguous")
         if x.is_cuda:
             st = torch.cuda.current_stream(x.device).cuda_stream
-            return x.data_ptr(), abi.MEM_DEVICE, tmap[x.dtype], st
-        return x.data_ptr(), abi.MEM_HOST, tmap[x.dtype], None
+            return x.data_ptr(), abi.MEM_DEVICE, _torch_dtype_code(x), st
+        return x.data_ptr(), abi.MEM_HOST, _torch_dtype_code(x), None
     a = x
     if not isinstance(a, np.ndarray) or not a.flags["C_CONTIGUOUS"]:
         raise ValueError("buffer must be a C-contiguous numpy array or a "
                          "contiguous torch tensor")
     return a.ctypes.data, abi.MEM_HOST, _NP2T[a.dtype], None
+
+
+class _Views(object):
+    """One side of a planar call as plane views (abi.PlaneView, include/
+    avirhip.h "Plane views"): the host array, the element type, the stream and
+    the tensors it points into. The library reads the array inside the call."""
+
+    def __init__(self, table, dt, stream, keep):
+        self.table = np.ascontiguousarray(table, dtype=np.int64)
+        self.count = int(self.table.shape[0])
+        self.ptr, self.dt, self.stream, self.keep = (
+            self.table.ctypes.data, dt, stream, keep)
+
+    @staticmethod
+    def _check(x, what):
+        if not (_is_torch(x) and x.is_cuda):
+            raise ValueError("%s: plane views take CUDA tensors (host memory "
+                             "behind a view is not supported)" % what)
+
+    @classmethod
+    def of_planes(cls, planes, w, h, what):
+        """A sequence of per-plane (H, W) CUDA tensors, each with its own
+        base, row stride and element stride."""
+        import torch
+        if len(planes) == 0:
+            raise ValueError("%s: no planes" % what)
+        rows = []
+        for t in planes:
+            cls._check(t, what)
+            if (tuple(t.shape) != (h, w) or t.dtype != planes[0].dtype
+                    or t.device != planes[0].device):
+                raise ValueError("%s: every plane must be a (%d, %d) tensor "
+                                 "of one dtype on one device" % (what, h, w))
+            sy, sx = (int(n) for n in t.stride())
+            if (h > 1 and sy < 1) or (w > 1 and sx < 1):
+                raise ValueError("%s: positive strides are required" % what)
+            rows.append((t.data_ptr(), sy if h > 1 else 0,
+                         sx if w > 1 else 1))
+        st = torch.cuda.current_stream(planes[0].device).cuda_stream
+        return cls(np.array(rows, dtype=np.int64).reshape(-1, 3),
+                   _torch_dtype_code(planes[0]), st, list(planes))
+
+    @classmethod
+    def of_tensor(cls, x, what):
+        """A (..., H, W) CUDA tensor with any positive strides: one view per
+        index of the leading dimensions, in C order."""
+        import torch
+        cls._check(x, what)
+        h, w = int(x.shape[-2]), int(x.shape[-1])
+        sy, sx = int(x.stride(-2)), int(x.stride(-1))
+        lead = [int(n) for n in x.shape[:-2]]
+        lstr = [int(n) for n in x.stride()[:-2]]
+        if ((h > 1 and sy < 1) or (w > 1 and sx < 1)
+                or any(n > 1 and q < 1 for n, q in zip(lead, lstr))):
+            raise ValueError("%s: positive strides are required" % what)
+        offs = np.zeros((1,), np.int64)
+        for n, q in zip(lead, lstr):
+            offs = (offs[:, None] + np.arange(n, dtype=np.int64)[None, :] * q
+                    ).reshape(-1)
+        tab = np.empty((offs.size, 3), np.int64)
+        tab[:, 0] = x.data_ptr() + offs * x.element_size()
+        tab[:, 1] = sy if h > 1 else 0
+        tab[:, 2] = sx if w > 1 else 1
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        return cls(tab, _torch_dtype_code(x), st, x)
+
+
+def _plane_side(x, w, h, what):
+    """One side of a planar call -> (pointer, mem kind, dtype code, stream,
+    views or None): a buffer as _buf takes it, or a sequence of per-plane
+    (H, W) CUDA tensors, which become plane views."""
+    if isinstance(x, (list, tuple)):
+        x = _Views.of_planes(x, w, h, what)
+    if isinstance(x, _Views):
+        return x.ptr, abi.MEM_VIEWS, x.dt, x.stream, x
+    return _buf(x) + (None,)
+
+
+def _device_of(x):
+    """The tensor a planar call's device is taken from."""
+    if isinstance(x, _Views):
+        x = x.keep
+    if isinstance(x, (list, tuple)):
+        x = x[0]
+    return x
+
+
+def _planes_operands(src, NewWidth, NewHeight, out_dtype, out):
+    """resize_planes' two sides -> (SrcBuf, NewBuf, result, h, w, n): today's
+    contiguous path where both are contiguous, plane views where a CUDA
+    tensor is not -- never a hidden copy."""
+    if len(src.shape) < 2:
+        raise ValueError("resize_planes: (..., H, W) expected")
+    lead = tuple(int(n) for n in src.shape[:-2])
+    h, w = int(src.shape[-2]), int(src.shape[-1])
+    n = 1
+    for d in lead:
+        n *= d
+    shape = lead + (NewHeight, NewWidth)
+    if out is not None and tuple(out.shape) != shape:
+        raise ValueError("resize_planes: out must have the shape %r"
+                         % (shape,))
+    if out is not None and _is_torch(out) != _is_torch(src):
+        raise ValueError("resize_planes: src and out must both be torch "
+                         "tensors or both numpy arrays")
+    if not _is_torch(src):
+        dst = out if out is not None else np.empty(shape,
+                                                   out_dtype or src.dtype)
+        return src, dst, dst, h, w, n
+    import torch
+    if out is None:
+        if src.is_contiguous():
+            out = torch.empty(shape, device=src.device,
+                              dtype=out_dtype or src.dtype)
+        else:
+            # the source's memory format: dense in its order of dimensions
+            order = sorted(range(len(shape)),
+                           key=lambda d: (-int(src.stride(d)), d))
+            out = torch.empty([shape[d] for d in order], device=src.device,
+                              dtype=out_dtype or src.dtype)
+            out = out.permute([order.index(d) for d in range(len(shape))])
+    sb = src if src.is_contiguous() else _Views.of_tensor(src, "src")
+    db = out if out.is_contiguous() else _Views.of_tensor(out, "out")
+    return sb, db, out, h, w, n
 
 
 class CImageResizerParams(abi.Params):
@@ -216,10 +345,20 @@ class CImageResizer(object):
         (avirhip_resizer_resize_planes): plane i of the result is, bit for
         bit, resizeImage(..., ElCountIO=1, k, aVars) of plane i of the source.
         Planes lie `SrcPlaneSize` / `NewPlaneSize` elements apart (0: tightly
-        packed); source rows at SrcScanlineSize, result rows tight."""
-        sp, sm, st, s1 = _buf(SrcBuf)
-        dp, dm, dt, s2 = _buf(NewBuf)
-        if min(SrcWidth, SrcHeight, NewWidth, NewHeight, PlaneCount) > 0:
+        packed); source rows at SrcScanlineSize, result rows tight. Either
+        buffer may instead be a sequence of PlaneCount per-plane (H, W) CUDA
+        tensors with any positive strides -- channel-last images, planes in
+        separate allocations -- which go in as plane views (its plane size
+        must then be 0)."""
+        sp, sm, st, s1, sv = _plane_side(SrcBuf, SrcWidth, SrcHeight, "SrcBuf")
+        dp, dm, dt, s2, dv = _plane_side(NewBuf, NewWidth, NewHeight, "NewBuf")
+        for v in (sv, dv):
+            if v is not None and v.count != PlaneCount:
+                raise ValueError("resizePlanes: %d plane views, PlaneCount %d"
+                                 % (v.count, PlaneCount))
+        if sv is not None or dv is not None:
+            pass    # (the library validates every view)
+        elif min(SrcWidth, SrcHeight, NewWidth, NewHeight, PlaneCount) > 0:
             ss = SrcScanlineSize if SrcScanlineSize >= 1 else SrcWidth
             sps = SrcPlaneSize if SrcPlaneSize != 0 else SrcHeight * ss
             nps = NewPlaneSize if NewPlaneSize != 0 else NewHeight * NewWidth
@@ -231,7 +370,7 @@ class CImageResizer(object):
             nps = NewPlaneSize if NewPlaneSize != 0 else NewHeight * NewWidth
             _need(NewBuf, (PlaneCount - 1) * nps + NewHeight * NewWidth,
                   "NewBuf")
-        with _on_device_of(SrcBuf, NewBuf):
+        with _on_device_of(_device_of(SrcBuf), _device_of(NewBuf)):
             abi.check(self._lib.avirhip_resizer_resize_planes(
                 self._h, sp, sm, SrcWidth, SrcHeight, SrcScanlineSize, dp, dm,
                 NewWidth, NewHeight, PlaneCount, SrcPlaneSize, NewPlaneSize,
@@ -239,24 +378,16 @@ class CImageResizer(object):
                 dt, s1 or s2), "avirhip_resizer_resize_planes")
 
     def resize_planes(self, src, NewWidth, NewHeight, k=0.0, out_dtype=None,
-                      aVars=None):
-        """src: a contiguous (..., H, W) array/tensor -> new (..., NewHeight,
-        NewWidth); all leading dimensions fold into the plane count."""
-        if len(src.shape) < 2:
-            raise ValueError("resize_planes: (..., H, W) expected")
-        lead = tuple(int(n) for n in src.shape[:-2])
-        h, w = int(src.shape[-2]), int(src.shape[-1])
-        n = 1
-        for d in lead:
-            n *= d
-        shape = lead + (NewHeight, NewWidth)
-        if _is_torch(src):
-            import torch
-            dst = torch.empty(shape, device=src.device,
-                              dtype=out_dtype or src.dtype)
-        else:
-            dst = np.empty(shape, out_dtype or src.dtype)
-        self.resizePlanes(src, w, h, 0, dst, NewWidth, NewHeight, n, 0, 0, k,
+                      aVars=None, out=None):
+        """src: a (..., H, W) array/tensor -> new (..., NewHeight, NewWidth);
+        all leading dimensions fold into the plane count. A CUDA tensor need
+        not be contiguous (channels_last, x.permute(0, 3, 1, 2) of an NHWC
+        tensor, slices: any positive strides): it is read where it lies, as
+        plane views, and the result keeps its memory format. `out`: the result
+        tensor, with the same freedom."""
+        sb, db, dst, h, w, n = _planes_operands(src, NewWidth, NewHeight,
+                                                out_dtype, out)
+        self.resizePlanes(sb, w, h, 0, db, NewWidth, NewHeight, n, 0, 0, k,
                           aVars)
         return dst
 
@@ -352,13 +483,21 @@ class CLancIR(object):
         (avirhip_lancir_resize_planes): plane i of the result is, bit for
         bit, resizeImage(..., ElCount=1) of plane i of the source. Planes lie
         `SrcPlaneSize` / `NewPlaneSize` elements apart (0: tightly packed);
-        rows at aParams.SrcSSize / NewSSize. Returns NewHeight, or 0 on a
-        parameter error."""
+        rows at aParams.SrcSSize / NewSSize. Either buffer may instead be a
+        sequence of PlaneCount per-plane (H, W) CUDA tensors with any positive
+        strides, which go in as plane views (its plane size must then be 0).
+        Returns NewHeight, or 0 on a parameter error."""
         if SrcBuf is None or NewBuf is None:
             return 0
-        sp, sm, st, s1 = _buf(SrcBuf)
-        dp, dm, dt, s2 = _buf(NewBuf)
-        if (min(SrcWidth, SrcHeight, NewWidth, NewHeight, PlaneCount) > 0
+        sp, sm, st, s1, sv = _plane_side(SrcBuf, SrcWidth, SrcHeight, "SrcBuf")
+        dp, dm, dt, s2, dv = _plane_side(NewBuf, NewWidth, NewHeight, "NewBuf")
+        for v in (sv, dv):
+            if v is not None and v.count != PlaneCount:
+                raise ValueError("resizePlanes: %d plane views, PlaneCount %d"
+                                 % (v.count, PlaneCount))
+        if sv is not None or dv is not None:
+            pass    # (the library validates every view)
+        elif (min(SrcWidth, SrcHeight, NewWidth, NewHeight, PlaneCount) > 0
                 and sp != dp):
             ss = aParams.SrcSSize if aParams is not None else 0
             ns = aParams.NewSSize if aParams is not None else 0
@@ -370,7 +509,7 @@ class CLancIR(object):
                   + SrcWidth, "SrcBuf")
             _need(NewBuf, (PlaneCount - 1) * nps + (NewHeight - 1) * ns
                   + NewWidth, "NewBuf")
-        with _on_device_of(SrcBuf, NewBuf):
+        with _on_device_of(_device_of(SrcBuf), _device_of(NewBuf)):
             rc = self._lib.avirhip_lancir_resize_planes(
                 self._h, sp, sm, SrcWidth, SrcHeight, dp, dm, NewWidth,
                 NewHeight, PlaneCount, SrcPlaneSize, NewPlaneSize,
@@ -379,24 +518,16 @@ class CLancIR(object):
         return abi.check(rc, "avirhip_lancir_resize_planes")
 
     def resize_planes(self, src, NewWidth, NewHeight, out_dtype=None,
-                      aParams=None):
-        """src: a contiguous (..., H, W) array/tensor -> new (..., NewHeight,
-        NewWidth); all leading dimensions fold into the plane count."""
-        if len(src.shape) < 2:
-            raise ValueError("resize_planes: (..., H, W) expected")
-        lead = tuple(int(n) for n in src.shape[:-2])
-        h, w = int(src.shape[-2]), int(src.shape[-1])
-        n = 1
-        for d in lead:
-            n *= d
-        shape = lead + (NewHeight, NewWidth)
-        if _is_torch(src):
-            import torch
-            dst = torch.empty(shape, device=src.device,
-                              dtype=out_dtype or src.dtype)
-        else:
-            dst = np.empty(shape, out_dtype or src.dtype)
-        rc = self.resizePlanes(src, w, h, dst, NewWidth, NewHeight, n, 0, 0,
+                      aParams=None, out=None):
+        """src: a (..., H, W) array/tensor -> new (..., NewHeight, NewWidth);
+        all leading dimensions fold into the plane count. A CUDA tensor need
+        not be contiguous (channels_last, permuted NHWC, slices: any positive
+        strides): it is read where it lies, as plane views, and the result
+        keeps its memory format. `out`: the result tensor, with the same
+        freedom."""
+        sb, db, dst, h, w, n = _planes_operands(src, NewWidth, NewHeight,
+                                                out_dtype, out)
+        rc = self.resizePlanes(sb, w, h, db, NewWidth, NewHeight, n, 0, 0,
                                aParams)
         if rc != NewHeight:
             raise AvirHipError("CLancIR.resizePlanes returned %d" % rc)

@@ -21,6 +21,8 @@ F16 = 5
 BF16 = 6
 EINVAL, ENODEV, EHIP, EUNSUPPORTED, ENOMEM, EINTERNAL = -1, -2, -3, -4, -5, -6
 MEM_HOST, MEM_DEVICE = 0, 1
+# planar calls: the side's pointer is a host array of PlaneView, one per plane
+MEM_VIEWS = 3
 
 STEP_FIR, STEP_UP_ZEROSTUFF, STEP_UP_FILTERED, STEP_RESIZE, STEP_RESIZE2 = range(5)
 STEP_NAMES = ["FIR", "UP_ZEROSTUFF", "UP_FILTERED", "RESIZE", "RESIZE2"]
@@ -134,6 +136,13 @@ class LancirParams(C.Structure):
     _fields_ = [("SrcSSize", C.c_int32), ("NewSSize", C.c_int32),
                 ("kx", C.c_double), ("ky", C.c_double),
                 ("ox", C.c_double), ("oy", C.c_double), ("la", C.c_double)]
+
+
+class PlaneView(C.Structure):
+    """avirhip_plane_view: element (r, c) of a plane is
+    base[r * row_pitch + c * elem_stride], in elements."""
+    _fields_ = [("base", C.c_void_p), ("row_pitch", C.c_longlong),
+                ("elem_stride", C.c_longlong)]
 
 
 # Every symbol include/avirhip.h declares: name -> (restype, argtypes)

@@ -109,6 +109,9 @@ struct ApParams
 	const int* hr; const int* vr;
 	int reg_a, reg_b; // first floats of the LDS regions A and B (F is at 0)
 	int use_tr; float tr_mul, tr_muli, pk_out;
+	// plane views (k_avirp< ., ., true >): plane i's source and result lie
+	// where views[ i ] says; src, dst and the four pitches above are not read
+	const PlaneViewDev* views;
 };
 
 // avir::round (avir.h:130-135) of the reference's x86-64 build, as generic.hip's
@@ -241,7 +244,10 @@ __device__ __forceinline__ void ap_op( const ApOp& op, const int o,
 	}
 }
 
-template< int SRC, int OUT >
+// VIEWS: as k_lancp's -- element (r, c) of a plane at base + r * pitch +
+// c * estride bytes from the table P.views; loader and store alone differ, and
+// the store stays a plain vector store of the element's own width.
+template< int SRC, int OUT, bool VIEWS >
 __global__ void __launch_bounds__( AP_NT ) k_avirp( const ApParams P )
 {
 	typedef typename ApElem< SRC > :: T src_t;
@@ -278,6 +284,14 @@ __global__ void __launch_bounds__( AP_NT ) k_avirp( const ApParams P )
 		va[ i ] = vr[ i ]; vn[ i ] = vr[ 4 + i ];
 	}
 
+	// (VIEWS: the plane's entry of the table; the dense form reads none of it)
+	PlaneViewDev vw = PlaneViewDev();
+
+	if constexpr( VIEWS )
+	{
+		vw = P.views[ plane ];
+	}
+
 	// LDS: F, the H chain's result for every source row of the tile (pitch
 	// tw), and the two regions the stages alternate between
 	const int rows = vn[ 0 ]; // source rows of the tile
@@ -294,19 +308,22 @@ __global__ void __launch_bounds__( AP_NT ) k_avirp( const ApParams P )
 		float* oth = B;
 
 		{
-			const char* const sp = P.src + (long) plane * P.src_sb +
-				(long) ha[ 0 ] * (long) sizeof( src_t );
+			const char* const sp = ( VIEWS ? vw.src :
+				P.src + (long) plane * P.src_sb ) + (long) ha[ 0 ] *
+				( VIEWS ? vw.src_eb : (long) sizeof( src_t ));
 			const int n = hn[ 0 ];
 
 			for( int r = wave; r < nr; r += AP_NT / 64 )
 			{
 				const char* const row = sp +
-					(long) ( va[ 0 ] + r0 + r ) * P.src_pb;
+					(long) ( va[ 0 ] + r0 + r ) *
+					( VIEWS ? vw.src_pb : P.src_pb );
 
 				for( int c = lane; c < n; c += 64 )
 				{
-					cur[ r * n + c ] = (float) *(const src_t*) ( row +
-						(long) c * (long) sizeof( src_t ));
+					cur[ r * n + c ] = (float) pview_load< VIEWS, src_t >( row +
+						(long) c *
+						( VIEWS ? vw.src_eb : (long) sizeof( src_t )));
 				}
 			}
 		}
@@ -398,9 +415,10 @@ __global__ void __launch_bounds__( AP_NT ) k_avirp( const ApParams P )
 
 				// the output stage (k_epilogue_px of generic.hip) in the store
 				float t = s[ 0 ];
-				out_t* const dp = (out_t*) ( P.dst + (long) plane * P.dst_sb +
-					(long) ( oa + r ) * P.dst_pb +
-					(long) j * (long) sizeof( out_t ));
+				char* const dp =
+					( VIEWS ? vw.dst : P.dst + (long) plane * P.dst_sb ) +
+					(long) ( oa + r ) * ( VIEWS ? vw.dst_pb : P.dst_pb ) +
+					(long) j * ( VIEWS ? vw.dst_eb : (long) sizeof( out_t ));
 
 				if constexpr( OUT == AP_U8 || OUT == AP_U16 )
 				{
@@ -411,7 +429,7 @@ __global__ void __launch_bounds__( AP_NT ) k_avirp( const ApParams P )
 
 				// (half: v_cvt_f16_f32, bfloat16: the compiler's conversion --
 				// both nearest even, denormals kept; float as it is)
-				*dp = (out_t) t;
+				pview_store< VIEWS, out_t >( dp, (out_t) t );
 			}
 
 			if( !last )
@@ -673,9 +691,11 @@ template< int SK >
 void ap_launch( const int ok, const long items, const size_t lds,
 	hipStream_t st, const ApParams& P, hipError_t* e )
 {
-#define AP_GO( OK ) { *e = AVIRHIP_DYN_LDS(( k_avirp< SK, OK > ), lds ); \
-		if( *e == hipSuccess ) hipLaunchKernelGGL(( k_avirp< SK, OK > ), \
+#define AP_GO1( OK, VW ) { *e = AVIRHIP_DYN_LDS(( k_avirp< SK, OK, VW > ), lds ); \
+		if( *e == hipSuccess ) hipLaunchKernelGGL(( k_avirp< SK, OK, VW > ), \
 		dim3( (unsigned) items ), dim3( AP_NT ), lds, st, P ); }
+#define AP_GO( OK ) { if( P.views != nullptr ) AP_GO1( OK, true ) \
+		else AP_GO1( OK, false ) }
 
 	switch( ok )
 	{
@@ -686,6 +706,7 @@ void ap_launch( const int ok, const long items, const size_t lds,
 		default: AP_GO( AP_F32 ); break;
 	}
 #undef AP_GO
+#undef AP_GO1
 }
 
 } // namespace
@@ -705,8 +726,9 @@ void avirp_release( avirhip_plan* p )
 
 // The planes of `p` (a CImageResizer plan of one channel): `n_planes` source
 // planes `src_ps` elements apart behind `src`, their results `dst_ps` elements
-// apart behind `dst`, rows at the plan's pitches; device memory, asynchronous
-// on `st`. 1: the call is not this kernel's, nothing was launched and `*why`
+// apart behind `dst`, rows at the plan's pitches -- or, with `views`, each
+// plane where its entry of that host table says (validated by the caller);
+// device memory, asynchronous on `st`. 1: the call is not this kernel's, nothing was launched and `*why`
 // says what it missed:
 //   element type        float64 on a side: no loader / store for it
 //   plan stages         sRGB gamma, the error-diffusion ditherer, fpclass_float4,
@@ -722,7 +744,8 @@ void avirp_release( avirhip_plan* p )
 //   AVIRHIP_AVIRP_OFF   set in the environment (read per call): the
 //                       measurement's switch for the per-plane road
 int avirp_run( avirhip_plan* p, const void* src, void* dst, long src_ps,
-	long dst_ps, int n_planes, hipStream_t st, const char** why )
+	long dst_ps, int n_planes, hipStream_t st, const char** why,
+	const PlaneViewTable* views )
 {
 	const int sk = gp_raw_kind( p -> in_type );
 	const int ok = gp_raw_kind( p -> out_type );
@@ -740,8 +763,9 @@ int avirp_run( avirhip_plan* p, const void* src, void* dst, long src_ps,
 		return( 1 );
 	}
 
-	if( (uintptr_t) src % dtype_size( p -> in_type ) != 0 ||
-		(uintptr_t) dst % dtype_size( p -> out_type ) != 0 )
+	if( views == nullptr &&
+		( (uintptr_t) src % dtype_size( p -> in_type ) != 0 ||
+		(uintptr_t) dst % dtype_size( p -> out_type ) != 0 ))
 	{
 		*why = "base alignment";
 		return( 1 );
@@ -816,6 +840,21 @@ int avirp_run( avirhip_plan* p, const void* src, void* dst, long src_ps,
 	P.tr_mul = (float) p -> tr_mul;
 	P.tr_muli = (float) ( 1.0 / p -> tr_mul );
 	P.pk_out = (float) p -> pk_out;
+	P.views = nullptr;
+	PlaneViewUpload up;
+
+	if( views != nullptr )
+	{
+		// (the last refusal is behind us: the table travels only to a launch)
+		const int rc = up.push( *views, p -> device, st );
+
+		if( rc != 0 )
+		{
+			return( rc );
+		}
+
+		P.views = up.dev();
+	}
 
 	if( getenv( "AVIRHIP_VERBOSE" ) != nullptr )
 	{
@@ -836,6 +875,7 @@ int avirp_run( avirhip_plan* p, const void* src, void* dst, long src_ps,
 		default: ap_launch< AP_F32 >( ok, items, lds, st, P, &e ); break;
 	}
 
+	up.done( st );
 	AVIRHIP_HIPCHECK( e );
 	AVIRHIP_HIPCHECK( hipGetLastError() );
 	return( AVIRHIP_OK );

@@ -1077,6 +1077,16 @@ struct DevBuf
 	~DevBuf() { if( p != nullptr ) (void) hipFree( p ); }
 };
 
+// a per-call device allocation in stream order: freed behind the work that
+// was enqueued on `st` before it goes out of scope, without waiting for it
+struct StreamBuf
+{
+	void* p;
+	hipStream_t st;
+	explicit StreamBuf( hipStream_t s ) : p( nullptr ), st( s ) {}
+	~StreamBuf() { if( p != nullptr ) (void) hipFreeAsync( p, st ); }
+};
+
 struct CurDevice
 {
 	int keep;
@@ -1090,6 +1100,447 @@ struct CurDevice
 	}
 	~CurDevice() { if( on ) (void) hipSetDevice( keep ); }
 };
+
+// ---- plane views (include/avirhip.h, "Plane views") ----------------------
+
+// One side of a planar call as it was given: a dense block of planes at a
+// plane stride, or (mem == AVIRHIP_MEM_VIEWS) a host array of views.
+struct ViewSideArg
+{
+	const char* what;
+	const void* ptr; int mem; long long stride;
+	int w, h; long pitch; // the call's own pitch in elements (< 1: the width)
+	int type;
+};
+
+// One plane of a side, resolved: where it lies, and its byte span [a, b).
+struct ViewRec
+{
+	const char* base; long pb, eb; // row pitch, element stride in bytes
+	long long P, E;                // ... in elements
+	uintptr_t a, b;
+};
+
+// Host arithmetic only: every rule of "Validation" for one side.
+int views_side( const ViewSideArg& A, const int n_planes,
+	std::vector< ViewRec >& out )
+{
+	const size_t es = dtype_size( A.type );
+	out.resize( (size_t) n_planes );
+
+	if( A.mem != AVIRHIP_MEM_VIEWS )
+	{
+		PlanesSide S;
+		const int rc = planes_side( A.what, A.w, A.h, A.pitch, A.stride,
+			n_planes, A.type, S );
+
+		if( rc != 0 )
+		{
+			return( rc );
+		}
+
+		if( (uintptr_t) A.ptr % es != 0 ||
+			(uintptr_t) A.ptr + S.span_bytes < (uintptr_t) A.ptr )
+		{
+			set_error( "planes: beside plane views the %s base must be a "
+				"multiple of the element size, its planes within the address "
+				"space", A.what );
+			return( AVIRHIP_EINVAL );
+		}
+
+		const size_t one = ( (size_t) ( A.h - 1 ) * S.pitch + A.w ) * es;
+
+		for( int i = 0; i < n_planes; i++ )
+		{
+			ViewRec& r = out[ (size_t) i ];
+			r.base = (const char*) A.ptr + (size_t) i * S.stride * es;
+			r.pb = (long) ( S.pitch * es ); r.eb = (long) es;
+			r.P = ( A.h > 1 ? S.pitch : 0 ); r.E = 1;
+			r.a = (uintptr_t) r.base; r.b = r.a + one;
+		}
+
+		return( AVIRHIP_OK );
+	}
+
+	if( A.stride != 0 )
+	{
+		set_error( "planes: %s plane stride %lld beside plane views (it must "
+			"be 0)", A.what, A.stride );
+		return( AVIRHIP_EINVAL );
+	}
+
+	const avirhip_plane_view* const v = (const avirhip_plane_view*) A.ptr;
+	typedef unsigned __int128 u128;
+	const u128 lim = (u128) UINTPTR_MAX;
+
+	for( int i = 0; i < n_planes; i++ )
+	{
+		ViewRec& r = out[ (size_t) i ];
+
+		if( v[ i ].base == nullptr )
+		{
+			set_error( "planes: %s view %d has a null base", A.what, i );
+			return( AVIRHIP_EINVAL );
+		}
+
+		if( v[ i ].row_pitch < 0 || v[ i ].elem_stride < 0 )
+		{
+			set_error( "planes: %s view %d: negative row pitch or element "
+				"stride (%lld, %lld)", A.what, i, v[ i ].row_pitch,
+				v[ i ].elem_stride );
+			return( AVIRHIP_EINVAL );
+		}
+
+		if( (uintptr_t) v[ i ].base % es != 0 )
+		{
+			set_error( "planes: %s view %d: the base is no multiple of the "
+				"element size %d", A.what, i, (int) es );
+			return( AVIRHIP_EINVAL );
+		}
+
+		const u128 E = (u128) std::max( v[ i ].elem_stride, 1LL );
+		const u128 row = (u128) ( A.w - 1 ) * E + 1;
+		const u128 P = ( v[ i ].row_pitch > 0 ? (u128) v[ i ].row_pitch :
+			E > 1 ? (u128) A.w * E :
+			(u128) ( A.pitch < 1 ? (long) A.w : A.pitch ));
+
+		if( A.h > 1 && P < row )
+		{
+			set_error( "planes: %s view %d: row pitch %lld is shorter than a "
+				"row (%lld elements)", A.what, i, (long long) P,
+				(long long) row );
+			return( AVIRHIP_EINVAL );
+		}
+
+		// (every factor is below 2^63, the products below 2^127)
+		const u128 bytes = ( (u128) ( A.h - 1 ) * P + row ) * es;
+
+		if( E > lim / es || P > lim / es || bytes > lim ||
+			(u128) (uintptr_t) v[ i ].base + bytes > lim )
+		{
+			set_error( "planes: %s view %d exceeds the address space", A.what,
+				i );
+			return( AVIRHIP_EINVAL );
+		}
+
+		r.base = (const char*) v[ i ].base;
+		r.pb = (long) ( P * es ); r.eb = (long) ( E * es );
+		// (a single row: the pitch addresses nothing and constrains nothing)
+		r.P = ( A.h > 1 ? (long long) P : 0 ); r.E = (long long) E;
+		r.a = (uintptr_t) r.base; r.b = r.a + (uintptr_t) bytes;
+	}
+
+	return( AVIRHIP_OK );
+}
+
+// "Overlap": a sort and a sweep on each question. Source spans are merged
+// into disjoint intervals and every result span looked up among them. Result
+// spans are swept by their starts: those still open at a start all hold that
+// byte, so they meet each other and the newcomer -- which must then be an
+// interleaved plane of theirs (the same P and E, P % E == 0, a base residue
+// mod E that none of them has; at most E spans are open at once).
+int views_overlap( const std::vector< ViewRec >& S,
+	const std::vector< ViewRec >& D )
+{
+	std::vector< std::pair< uintptr_t, uintptr_t > > u;
+
+	for( const ViewRec& r : S )
+	{
+		u.push_back( std::make_pair( r.a, r.b ));
+	}
+
+	std::sort( u.begin(), u.end() );
+	size_t m = 0;
+
+	for( size_t i = 0; i < u.size(); i++ )
+	{
+		if( m > 0 && u[ i ].first <= u[ m - 1 ].second )
+		{
+			u[ m - 1 ].second = std::max( u[ m - 1 ].second, u[ i ].second );
+		}
+		else
+		{
+			u[ m++ ] = u[ i ];
+		}
+	}
+
+	u.resize( m );
+
+	for( const ViewRec& r : D )
+	{
+		// the first merged interval that ends behind r.a
+		size_t lo = 0, hi = u.size();
+
+		while( lo < hi )
+		{
+			const size_t mid = ( lo + hi ) / 2;
+
+			if( u[ mid ].second > r.a ) hi = mid; else lo = mid + 1;
+		}
+
+		if( lo < u.size() && u[ lo ].first < r.b )
+		{
+			set_error( "planes: source and result planes share bytes" );
+			return( AVIRHIP_EINVAL );
+		}
+	}
+
+	std::vector< const ViewRec* > d;
+
+	for( const ViewRec& r : D )
+	{
+		d.push_back( &r );
+	}
+
+	std::sort( d.begin(), d.end(), []( const ViewRec* x, const ViewRec* y )
+		{ return( x -> a < y -> a ); } );
+
+	// the open spans: a heap by end, and their residues
+	std::vector< std::pair< uintptr_t, long long > > open; // (end, residue)
+	std::vector< long long > res;
+	const auto later = []( const std::pair< uintptr_t, long long >& x,
+		const std::pair< uintptr_t, long long >& y )
+		{ return( x.first > y.first ); };
+	long long oP = 0, oE = 0;
+
+	for( const ViewRec* const r : d )
+	{
+		while( !open.empty() && open.front().first <= r -> a )
+		{
+			res.erase( std::find( res.begin(), res.end(),
+				open.front().second ));
+			std::pop_heap( open.begin(), open.end(), later );
+			open.pop_back();
+		}
+
+		const long long es = r -> eb / r -> E;
+		const long long q = (long long) (( r -> a / (uintptr_t) es ) %
+			(uintptr_t) r -> E );
+
+		if( !open.empty() )
+		{
+			if( r -> P != oP || r -> E != oE || r -> P % r -> E != 0 ||
+				std::find( res.begin(), res.end(), q ) != res.end() )
+			{
+				set_error( "planes: result views share bytes and are not "
+					"interleaved planes (the same row pitch P and element "
+					"stride E, P %% E == 0, bases not a multiple of E apart)" );
+				return( AVIRHIP_EINVAL );
+			}
+		}
+
+		oP = r -> P; oE = r -> E;
+		open.push_back( std::make_pair( r -> b, q ));
+		std::push_heap( open.begin(), open.end(), later );
+		res.push_back( q );
+	}
+
+	return( AVIRHIP_OK );
+}
+
+// Both sides of a call with plane views on at least one of them: validated,
+// and resolved into the kernels' table. `with_src` false: a zero-sized source
+// (the result side alone is checked and resolved).
+int views_layout( const ViewSideArg& SA, const ViewSideArg& DA,
+	const int n_planes, const bool with_src, PlaneViewTable& tab )
+{
+	std::vector< ViewRec > S, D;
+
+	for( const ViewSideArg* const A : { &SA, &DA })
+	{
+		if( A -> ptr == nullptr && ( with_src || A == &DA ))
+		{
+			set_error( "planes: null %s", A -> what );
+			return( AVIRHIP_EINVAL );
+		}
+
+		if( A -> mem == AVIRHIP_MEM_HOST )
+		{
+			set_error( "planes: beside plane views the %s must be device "
+				"memory", A -> what );
+			return( AVIRHIP_EINVAL );
+		}
+	}
+
+	int rc = views_side( DA, n_planes, D );
+	if( rc == 0 && with_src ) rc = views_side( SA, n_planes, S );
+	if( rc == 0 ) rc = views_overlap( S, D );
+
+	if( rc != 0 )
+	{
+		return( rc );
+	}
+
+	tab.resize( (size_t) n_planes );
+
+	for( int i = 0; i < n_planes; i++ )
+	{
+		PlaneViewDev& t = tab[ (size_t) i ];
+		t.src = nullptr; t.src_pb = 0; t.src_eb = 0;
+
+		if( with_src )
+		{
+			t.src = S[ (size_t) i ].base; t.src_pb = S[ (size_t) i ].pb;
+			t.src_eb = S[ (size_t) i ].eb;
+		}
+
+		t.dst = (char*) D[ (size_t) i ].base; t.dst_pb = D[ (size_t) i ].pb;
+		t.dst_eb = D[ (size_t) i ].eb;
+	}
+
+	return( AVIRHIP_OK );
+}
+
+// A zero-sized source: every result view zero-filled row by row, its
+// elements alone.
+int views_zero_fill( const PlaneViewTable& tab, const void* dst,
+	const int dst_mem, const int w, const int h, const int type,
+	hipStream_t st )
+{
+	const size_t es = dtype_size( type );
+
+	// (validation is behind us: the first call that may reach the device)
+	if( dst_mem == AVIRHIP_MEM_AUTO &&
+		avirhip_resolve_mem( dst, dst_mem ) == AVIRHIP_MEM_HOST )
+	{
+		set_error( "planes: beside plane views the result must be device "
+			"memory" );
+		return( AVIRHIP_EINVAL );
+	}
+
+	for( const PlaneViewDev& t : tab )
+	{
+		if( (size_t) t.dst_eb == es )
+		{
+			// (one row is its own pitch: a last row may end the allocation)
+			AVIRHIP_HIPCHECK( hipMemset2DAsync( t.dst, h > 1 ? (size_t) t.dst_pb :
+				(size_t) w * es, 0, (size_t) w * es, h, st ));
+			continue;
+		}
+
+		for( int y = 0; y < h; y++ )
+		{
+			// a row as w "rows" of one element at a pitch of the stride
+			AVIRHIP_HIPCHECK( hipMemset2DAsync( t.dst + (size_t) y * t.dst_pb,
+				w > 1 ? (size_t) t.dst_eb : es, 0, es, w, st ));
+		}
+	}
+
+	return( AVIRHIP_OK );
+}
+
+inline bool has_views( const int src_mem, const int dst_mem )
+{
+	return( src_mem == AVIRHIP_MEM_VIEWS || dst_mem == AVIRHIP_MEM_VIEWS );
+}
+
+// avirhip_resize_planes with plane views on at least one side.
+int planes_views_run( avirhip_plan* p, const void* src, int src_mem,
+	long long src_plane_stride, void* dst, int dst_mem,
+	long long dst_plane_stride, int n_planes, void* stream )
+{
+	const ViewSideArg SA = { "source", src, src_mem, src_plane_stride,
+		p -> src_w, p -> src_h, p -> src_stride, p -> in_type };
+	const ViewSideArg DA = { "result", dst, dst_mem, dst_plane_stride,
+		p -> new_w, p -> new_h, p -> new_stride, p -> out_type };
+	PlaneViewTable tab;
+	int rc = views_layout( SA, DA, n_planes, true, tab );
+
+	if( rc != 0 )
+	{
+		return( rc );
+	}
+
+	// (validation is behind us: the first call that may reach the device)
+	if(( src_mem == AVIRHIP_MEM_AUTO &&
+		avirhip_resolve_mem( src, src_mem ) == AVIRHIP_MEM_HOST ) ||
+		( dst_mem == AVIRHIP_MEM_AUTO &&
+		avirhip_resolve_mem( dst, dst_mem ) == AVIRHIP_MEM_HOST ))
+	{
+		set_error( "planes: beside plane views the other side must be device "
+			"memory" );
+		return( AVIRHIP_EINVAL );
+	}
+
+	hipStream_t st = (hipStream_t) stream;
+	CurDevice dev( p -> device );
+	const char* why = "";
+	rc = ( p -> is_lancir ?
+		lancp_run( p, nullptr, nullptr, 0, 0, n_planes, st, &why, &tab ) :
+		avirp_run( p, nullptr, nullptr, 0, 0, n_planes, st, &why, &tab ));
+
+	if( rc != 1 )
+	{
+		return( rc );
+	}
+
+	// The plan's own road, plane by plane. It reads and writes tight planes at
+	// the plan's pitches: a view that is one passes its base; any other is
+	// gathered into / scattered from a per-call buffer (one plane a side,
+	// used again by the next plane behind it on the stream).
+	if( getenv( "AVIRHIP_VERBOSE" ) != nullptr )
+	{
+		fprintf( stderr, "planes: per-plane road (%s)\n", why );
+	}
+
+	const long ses = (long) dtype_size( p -> in_type );
+	const long oes = (long) dtype_size( p -> out_type );
+	const long spb = (long) p -> src_stride * ses;
+	const long dpb = (long) p -> new_stride * oes;
+	bool stage_s = false, stage_d = false;
+
+	for( const PlaneViewDev& t : tab )
+	{
+		stage_s = stage_s || t.src_eb != ses || ( p -> src_h > 1 && t.src_pb != spb );
+		stage_d = stage_d || t.dst_eb != oes || ( p -> new_h > 1 && t.dst_pb != dpb );
+	}
+
+	// (stream-ordered: allocated and freed behind the work on `st`, so that
+	// this road waits for the device no more than the plan's own does)
+	StreamBuf bs( st ), bd( st );
+
+	if( stage_s )
+	{
+		AVIRHIP_HIPCHECK( hipMallocAsync( &bs.p, (size_t) p -> src_h * spb,
+			st ));
+	}
+
+	if( stage_d )
+	{
+		AVIRHIP_HIPCHECK( hipMallocAsync( &bd.p, (size_t) p -> new_h * dpb,
+			st ));
+	}
+
+	rc = AVIRHIP_OK;
+
+	for( int i = 0; i < n_planes && rc == 0; i++ )
+	{
+		const PlaneViewDev& t = tab[ (size_t) i ];
+		const bool gs = ( t.src_eb != ses || ( p -> src_h > 1 && t.src_pb != spb ));
+		const bool sd = ( t.dst_eb != oes || ( p -> new_h > 1 && t.dst_pb != dpb ));
+
+		if( gs )
+		{
+			rc = pview_copy( t.src, t.src_pb, t.src_eb, bs.p, spb, ses,
+				p -> src_w, p -> src_h, (int) ses, st );
+		}
+
+		if( rc == 0 )
+		{
+			rc = avirhip_resize( p, gs ? bs.p : (const void*) t.src,
+				AVIRHIP_MEM_DEVICE, sd ? bd.p : (void*) t.dst,
+				AVIRHIP_MEM_DEVICE, stream );
+		}
+
+		if( rc == 0 && sd )
+		{
+			rc = pview_copy( bd.p, dpb, oes, t.dst, t.dst_pb, t.dst_eb,
+				p -> new_w, p -> new_h, (int) oes, st );
+		}
+	}
+
+	return( rc );
+}
 
 } // namespace
 
@@ -1119,6 +1570,12 @@ try
 	{
 		set_error( "resize_planes: n_planes %d", n_planes );
 		return( AVIRHIP_EINVAL );
+	}
+
+	if( has_views( src_mem, dst_mem ))
+	{
+		return( planes_views_run( p, src, src_mem, src_plane_stride, dst,
+			dst_mem, dst_plane_stride, n_planes, stream ));
 	}
 
 	PlanesSide S, D;
@@ -1237,6 +1694,37 @@ try
 
 	// the stride rule and the overlap rule, before any plan exists
 	const bool empty = ( src_w == 0 || src_h == 0 );
+	if( has_views( src_mem, dst_mem ))
+	{
+		const ViewSideArg SA = { "source", src, src_mem, src_plane_stride,
+			src_w, src_h, params != nullptr ? params -> SrcSSize : 0, in_type };
+		const ViewSideArg DA = { "result", dst, dst_mem, dst_plane_stride,
+			new_w, new_h, params != nullptr ? params -> NewSSize : 0, out_type };
+		PlaneViewTable tab;
+		int rc = views_layout( SA, DA, n_planes, !empty, tab );
+
+		if( rc == 0 && empty )
+		{
+			rc = views_zero_fill( tab, dst, dst_mem, new_w, new_h, out_type,
+				(hipStream_t) stream );
+			return( rc != 0 ? rc : new_h );
+		}
+
+		avirhip_plan* p = nullptr;
+		if( rc == 0 ) rc = lancir_acquire( l, src_w, src_h, new_w, new_h, 1,
+			params, in_type, out_type, false, &p );
+
+		if( rc != 0 )
+		{
+			return( rc );
+		}
+
+		rc = avirhip_resize_planes( p, src, src_mem, src_plane_stride, dst,
+			dst_mem, dst_plane_stride, n_planes, stream );
+		lancir_release( l, p );
+		return( rc != 0 ? rc : new_h );
+	}
+
 	PlanesSide S, D;
 	int rc = planes_side( "result", new_w, new_h,
 		params != nullptr ? params -> NewSSize : 0, dst_plane_stride, n_planes,
@@ -1332,6 +1820,42 @@ try
 		{
 			set_error( "resizer_resize_planes: null image" );
 			return( AVIRHIP_EINVAL );
+		}
+
+		if( has_views( src_mem, dst_mem ))
+		{
+			if( new_w == 0 || new_h == 0 )
+			{
+				return( AVIRHIP_OK );
+			}
+
+			const ViewSideArg SA = { "source", src, src_mem, src_plane_stride,
+				src_w, src_h, src_scanline_size, in_type };
+			const ViewSideArg DA = { "result", dst, dst_mem, dst_plane_stride,
+				new_w, new_h, 0, out_type };
+			PlaneViewTable tab;
+			int rc = views_layout( SA, DA, n_planes, !empty, tab );
+
+			if( rc == 0 && empty )
+			{
+				return( views_zero_fill( tab, dst, dst_mem, new_w, new_h,
+					out_type, (hipStream_t) stream ));
+			}
+
+			avirhip_plan* p = nullptr;
+			if( rc == 0 ) rc = resizer_acquire( r, src_w, src_h,
+				src_scanline_size, new_w, new_h, 1, k, vars, in_type, out_type,
+				false, &p );
+
+			if( rc != 0 )
+			{
+				return( rc );
+			}
+
+			rc = avirhip_resize_planes( p, src, src_mem, src_plane_stride,
+				dst, dst_mem, dst_plane_stride, n_planes, stream );
+			resizer_release( r, p );
+			return( rc );
 		}
 
 		// the stride rule and the overlap rule, before any plan exists

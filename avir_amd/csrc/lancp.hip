@@ -42,7 +42,9 @@
 // pass stores consecutive ones.
 // Row and plane addresses are formed in 64 bits
 // ( base + (long) plane * stride + (long) row * pitch ): no distance limit
-// exists and the host checks none.
+// exists and the host checks none. With plane views (AVIRHIP_MEM_VIEWS) a
+// plane's base, row pitch and element stride come from a table instead, by
+// plane: the VIEWS instantiation below, whose loader and store alone differ.
 //
 // The kernel allocates nothing and uses no scratch of the plan: calls on one
 // plan need no lock.
@@ -85,6 +87,9 @@ struct LancpParams
 	const int* hstart; const int* hfidx; const float* hflt; int hkl;
 	int unity; float out_mul, clampv;
 	int l4;        // new_w & ~3: the elements that round to nearest even
+	// plane views (k_lancp< ., ., true >): plane i's source and result lie
+	// where views[ i ] says; src, dst and the four pitches above are not read
+	const PlaneViewDev* views;
 };
 
 // position of column x in an intermediate row (see "LDS banks" above)
@@ -93,7 +98,14 @@ __device__ __forceinline__ int lp_skew( const int x )
 	return( x + ( x >> 5 ));
 }
 
-template< int SRC, int OUT >
+// VIEWS: element (r, c) of a plane lies at base + r * pitch + c * estride
+// bytes, the three read from the table P.views by plane (one load of 48 bytes
+// per workgroup, uniform: scalar). Everything between the loader and the
+// store is the dense form's. The store stays a plain vector store of the
+// element's own width: interleaved result planes are written by other
+// workgroups, on other XCDs, into the same cache lines, whose L2s keep dirty
+// bytes apart -- a store widened to its neighbours would write them back stale.
+template< int SRC, int OUT, bool VIEWS >
 __global__ void __launch_bounds__( LP_NT ) k_lancp( const LancpParams P )
 {
 	typedef typename LpElem< SRC > :: T src_t;
@@ -130,7 +142,16 @@ __global__ void __launch_bounds__( LP_NT ) k_lancp( const LancpParams P )
 	const int cx1 = min( max( P.hstart[ j1 - 1 ] + hkl - 1, 0 ), P.sw - 1 );
 	const int S = cx1 - cx0 + 1;
 
-	const char* const splane = P.src + (long) plane * P.src_sb;
+	// (VIEWS: the plane's entry of the table; the dense form reads none of it)
+	PlaneViewDev vw = PlaneViewDev();
+
+	if constexpr( VIEWS )
+	{
+		vw = P.views[ plane ];
+	}
+
+	const char* const splane = ( VIEWS ? vw.src :
+		P.src + (long) plane * P.src_sb );
 
 	// the H pass' own position and phase: loaded here, so that they travel
 	// while the V pass runs
@@ -169,13 +190,14 @@ __global__ void __launch_bounds__( LP_NT ) k_lancp( const LancpParams P )
 
 		for( int c = lane; c < S; c += 64 )
 		{
-			const char* const col = splane +
-				(long) ( cx0 + c ) * (long) sizeof( src_t );
+			const char* const col = splane + (long) ( cx0 + c ) *
+				( VIEWS ? vw.src_eb : (long) sizeof( src_t ));
 
 			auto px = [&]( const int t ) -> float
 			{
 				const int yy = min( max( st + t, 0 ), P.sh - 1 );
-				return( (float) *(const src_t*) ( col + (long) yy * P.src_pb ));
+				return( (float) pview_load< VIEWS, src_t >( col + (long) yy *
+					( VIEWS ? vw.src_pb : P.src_pb )));
 			};
 
 			float s0 = f[ 0 ] * px( 0 ), s1 = f[ 1 ] * px( 1 );
@@ -277,8 +299,8 @@ __global__ void __launch_bounds__( LP_NT ) k_lancp( const LancpParams P )
 	}
 
 	// ---- gain, output stage by position, store
-	char* const dcol = P.dst + (long) plane * P.dst_sb +
-		(long) j * (long) sizeof( out_t );
+	char* const dcol = ( VIEWS ? vw.dst : P.dst + (long) plane * P.dst_sb ) +
+		(long) j * ( VIEWS ? vw.dst_eb : (long) sizeof( out_t ));
 #pragma unroll
 	for( int i = 0; i < NR; i++ )
 	{
@@ -296,7 +318,7 @@ __global__ void __launch_bounds__( LP_NT ) k_lancp( const LancpParams P )
 			v = v * P.out_mul;
 		}
 
-		out_t* const op = (out_t*) ( dcol + (long) y * P.dst_pb );
+		char* const op = dcol + (long) y * ( VIEWS ? vw.dst_pb : P.dst_pb );
 
 		if constexpr( OUT == LP_U8 || OUT == LP_U16 )
 		{
@@ -304,19 +326,19 @@ __global__ void __launch_bounds__( LP_NT ) k_lancp( const LancpParams P )
 			{
 				v = ( v < P.clampv ? v : P.clampv );
 				v = ( v > 0.0f ? v : 0.0f );
-				*op = (out_t) (int) rintf( v );
+				pview_store< VIEWS, out_t >( op, (out_t) (int) rintf( v ));
 			}
 			else
 			{
-				*op = (out_t) (int) (( v > P.clampv ? P.clampv :
-					( v < 0.0f ? 0.0f : v )) + 0.5f );
+				pview_store< VIEWS, out_t >( op, (out_t) (int) (( v > P.clampv ?
+					P.clampv : ( v < 0.0f ? 0.0f : v )) + 0.5f ));
 			}
 		}
 		else
 		{
 			// (float as it is; half: v_cvt_f16_f32, bfloat16: the compiler's
 			// conversion -- both nearest even, as k_lancir_out's (Tout) v)
-			*op = (out_t) v;
+			pview_store< VIEWS, out_t >( op, (out_t) v );
 		}
 	}
 }
@@ -327,11 +349,14 @@ __global__ void __launch_bounds__( LP_NT ) k_lancp( const LancpParams P )
 
 // The planes of `p` (a CLancIR plan of one channel): `n_planes` source planes
 // `src_ps` elements apart behind `src`, their results `dst_ps` elements apart
-// behind `dst`, rows at the plan's pitches; device memory, asynchronous on
+// behind `dst`, rows at the plan's pitches -- or, with `views`, each plane
+// where its entry of that host table says (src, dst and the strides are not
+// used; the caller has validated the table); device memory, asynchronous on
 // `st`. 1: the call is not this kernel's, nothing was launched and `*why`
 // says what it missed.
 int lancp_run( const avirhip_plan* p, const void* src, void* dst, long src_ps,
-	long dst_ps, int n_planes, hipStream_t st, const char** why )
+	long dst_ps, int n_planes, hipStream_t st, const char** why,
+	const PlaneViewTable* views )
 {
 	const int sk = gp_raw_kind( p -> in_type );
 	const int ok = gp_raw_kind( p -> out_type );
@@ -342,8 +367,9 @@ int lancp_run( const avirhip_plan* p, const void* src, void* dst, long src_ps,
 		return( 1 );
 	}
 
-	if( (uintptr_t) src % dtype_size( p -> in_type ) != 0 ||
-		(uintptr_t) dst % dtype_size( p -> out_type ) != 0 )
+	if( views == nullptr &&
+		( (uintptr_t) src % dtype_size( p -> in_type ) != 0 ||
+		(uintptr_t) dst % dtype_size( p -> out_type ) != 0 ))
 	{
 		*why = "base alignment";
 		return( 1 );
@@ -421,6 +447,21 @@ int lancp_run( const avirhip_plan* p, const void* src, void* dst, long src_ps,
 	P.unity = p -> l_unity; P.out_mul = p -> l_out_mul;
 	P.clampv = p -> l_clamp;
 	P.l4 = p -> new_w & ~3;
+	P.views = nullptr;
+	PlaneViewUpload up;
+
+	if( views != nullptr )
+	{
+		// (the last refusal is behind us: the table travels only to a launch)
+		const int rc = up.push( *views, p -> device, st );
+
+		if( rc != 0 )
+		{
+			return( rc );
+		}
+
+		P.views = up.dev();
+	}
 
 	if( getenv( "AVIRHIP_VERBOSE" ) != nullptr )
 	{
@@ -428,8 +469,11 @@ int lancp_run( const avirhip_plan* p, const void* src, void* dst, long src_ps,
 			"lds %d)\n", items, n_planes, LP_TW, LP_TR, span, (int) lds );
 	}
 
-#define LP_LAUNCH( SK, OK ) hipLaunchKernelGGL(( k_lancp< SK, OK > ), \
-		dim3( (unsigned) items ), dim3( LP_NT ), lds, st, P )
+#define LP_LAUNCH( SK, OK ) { if( P.views != nullptr ) \
+		hipLaunchKernelGGL(( k_lancp< SK, OK, true > ), \
+		dim3( (unsigned) items ), dim3( LP_NT ), lds, st, P ); else \
+		hipLaunchKernelGGL(( k_lancp< SK, OK, false > ), \
+		dim3( (unsigned) items ), dim3( LP_NT ), lds, st, P ); }
 #define LP_OUT( SK ) switch( ok ) { \
 		case LP_U8: LP_LAUNCH( SK, LP_U8 ); break; \
 		case LP_U16: LP_LAUNCH( SK, LP_U16 ); break; \
@@ -448,6 +492,7 @@ int lancp_run( const avirhip_plan* p, const void* src, void* dst, long src_ps,
 #undef LP_OUT
 #undef LP_LAUNCH
 
+	up.done( st );
 	AVIRHIP_HIPCHECK( hipGetLastError() );
 	return( AVIRHIP_OK );
 }

@@ -609,15 +609,90 @@ bool lanc2h_image_ok( const void* ptr, int type, long stride );
 int lanc2h_run( const avirhip_plan* q, const ImageRef& src,
 	const LancirOut& out, int row0, int row1, hipStream_t st );
 
+// pviews.hip: plane views (include/avirhip.h, "Plane views"). One plane of a
+// planar call as k_lancp / k_avirp read it from their table: where the source
+// and the result plane lie, pitches and element strides in BYTES.
+struct PlaneViewDev
+{
+	const char* src; long src_pb, src_eb;
+	char* dst; long dst_pb, dst_eb;
+};
+
+typedef std::vector< PlaneViewDev > PlaneViewTable;
+
+// The way of a call's table to the device: a slot of a process-wide pool (a
+// pinned host buffer, a device buffer, an event) is taken under the pool's
+// mutex, which is held for the search alone; the table is copied into the
+// pinned buffer -- the caller's array is free from then on -- and from there to
+// the device buffer on the call's stream; done() records the slot's event
+// behind the launch and hands the slot back, to be taken again once the event
+// has passed. No call waits for the device, no two calls share a buffer, no
+// plan owns one: calls on one plan from several threads stay lock-free.
+class PlaneViewUpload
+{
+public:
+	PlaneViewUpload() : slot( nullptr ), pushed( nullptr ) {}
+	~PlaneViewUpload(); // a call that failed behind push(): done() on its stream
+	int push( const PlaneViewTable& t, int device, hipStream_t st );
+	const PlaneViewDev* dev() const;
+	void done( hipStream_t st );
+
+private:
+	void* slot;
+	hipStream_t pushed;
+};
+
+// Loads and stores of the VIEWS kernels: a base read from the table is a
+// generic pointer to the compiler (flat_load / flat_store, which count with
+// the LDS traffic); it is device memory by contract, and said so here
+// (global_load / global_store). G false: the plain access of the dense forms,
+// whose bases are kernel arguments and global already.
+#if defined( __HIPCC__ )
+template< bool G, typename T >
+__device__ __forceinline__ T pview_load( const char* const p )
+{
+	if constexpr( G )
+	{
+		return( *(const __attribute__(( address_space( 1 ))) T*) p );
+	}
+	else
+	{
+		return( *(const T*) p );
+	}
+}
+
+template< bool G, typename T >
+__device__ __forceinline__ void pview_store( char* const p, const T v )
+{
+	if constexpr( G )
+	{
+		*(__attribute__(( address_space( 1 ))) T*) p = v;
+	}
+	else
+	{
+		*(T*) p = v;
+	}
+}
+#endif
+
+// strided <-> tight copy of ONE plane in elements of `es` bytes (1, 2, 4, 8):
+// element (r, c) goes from src + r * s_pb + c * s_eb to dst + r * d_pb +
+// c * d_eb; nothing else is written. The gather and the scatter of the
+// per-plane road of views.
+int pview_copy( const void* src, long s_pb, long s_eb, void* dst, long d_pb,
+	long d_eb, int w, int h, int es, hipStream_t st );
+
 // lancp.hip: the planes of a CLancIR plan of one channel (avirhip_resize_planes)
 // in one launch, one float per lane: `n_planes` source planes `src_ps` elements
 // apart, their results `dst_ps` elements apart, rows at the plan's pitches,
 // device memory. 1: the call is not its own (an element type outside uint8,
 // uint16, float, half, bfloat16; a base that is no multiple of the element
 // size; a tile of intermediate rows that exceeds its LDS) and `*why` names
-// what it missed; the caller runs the plan's own road per plane.
+// what it missed; the caller runs the plan's own road per plane. `views`
+// (host, validated, or nullptr): every plane where its entry says instead.
 int lancp_run( const avirhip_plan* p, const void* src, void* dst, long src_ps,
-	long dst_ps, int n_planes, hipStream_t st, const char** why );
+	long dst_ps, int n_planes, hipStream_t st, const char** why,
+	const PlaneViewTable* views = nullptr );
 
 // avirp.hip: the same for a CImageResizer plan of one channel -- k_avirp runs
 // the plan's lowered ops of both axes on LDS tiles, all planes in one launch.
@@ -626,7 +701,8 @@ int lancp_run( const avirhip_plan* p, const void* src, void* dst, long src_ps,
 // size; a chain of more than three ops; no tile within its LDS) and `*why`
 // names what it missed. avirp_release frees what the first call made.
 int avirp_run( avirhip_plan* p, const void* src, void* dst, long src_ps,
-	long dst_ps, int n_planes, hipStream_t st, const char** why );
+	long dst_ps, int n_planes, hipStream_t st, const char** why,
+	const PlaneViewTable* views = nullptr );
 void avirp_release( avirhip_plan* p );
 
 } // namespace avirhip

@@ -335,6 +335,35 @@ public:
 			NewWidth, NewHeight, 1, k );
 	}
 
+	/* The same call over plane views (avirhip.h, "Plane views"): SrcViews and
+	 * NewViews are host arrays of PlaneCount avirhip_plane_view, each a
+	 * device base, a row pitch and an element stride -- one HWC RGB image is
+	 * three views { img + c, W * 3, 3 }. Tin and Tout, the element types
+	 * behind the views, are given explicitly:
+	 * R.resizeImagePlanes< uint8_t, float >( sv, ... ). The arrays may be
+	 * reused as soon as the call returns. */
+	template< typename Tin, typename Tout >
+	void resizeImagePlanes( const avirhip_plane_view* const SrcViews,
+		const int SrcWidth, const int SrcHeight,
+		const avirhip_plane_view* const NewViews, const int NewWidth,
+		const int NewHeight, const int PlaneCount, const double k,
+		CImageResizerVars* const aVars = nullptr, void* const stream = nullptr )
+		const
+	{
+		avirhip_vars v;
+		varsIn( aVars, 1, v );
+
+		hipdetail :: check( avirhip_resizer_resize_planes( h, SrcViews,
+			AVIRHIP_MEM_VIEWS, SrcWidth, SrcHeight, 0, (void*) NewViews,
+			AVIRHIP_MEM_VIEWS, NewWidth, NewHeight, PlaneCount, 0, 0, k, &v,
+			hipdetail :: dtype_of< Tin > :: v,
+			hipdetail :: dtype_of< Tout > :: v, stream ),
+			"avir::CImageResizer::resizeImagePlanes" );
+
+		varsOut< Tin, Tout >( aVars, v, SrcWidth, SrcHeight, 0, NewWidth,
+			NewHeight, 1, k );
+	}
+
 private:
 	/* the caller-settable fields of *aVars for the C ABI, and the fpclass
 	 * fields the call writes into *aVars up front */

@@ -179,6 +179,52 @@ public:
 		return( rc );
 	}
 
+	/* The same call over plane views (avirhip.h, "Plane views"): SrcViews and
+	 * NewViews are host arrays of PlaneCount avirhip_plane_view, each a
+	 * device base, a row pitch and an element stride -- one HWC RGB image is
+	 * three views { img + c, W * 3, 3 }. Tin and Tout, the element types
+	 * behind the views, are given explicitly:
+	 * L.resizeImagePlanes< uint8_t, float >( sv, ... ). A view's row_pitch
+	 * of 0 takes aParams' SrcSSize / NewSSize. The arrays may be reused as
+	 * soon as the call returns. */
+	template< typename Tin, typename Tout >
+	int resizeImagePlanes( const avirhip_plane_view* const SrcViews,
+		const int SrcWidth, const int SrcHeight,
+		const avirhip_plane_view* const NewViews, const int NewWidth,
+		const int NewHeight, const int PlaneCount,
+		const CLancIRParams* const aParams = nullptr,
+		void* const stream = nullptr )
+	{
+		avirhip_lancir_params p;
+		avirhip_lancir_params_default( &p );
+
+		if( aParams != nullptr )
+		{
+			p.SrcSSize = aParams -> SrcSSize; p.NewSSize = aParams -> NewSSize;
+			p.kx = aParams -> kx; p.ky = aParams -> ky;
+			p.ox = aParams -> ox; p.oy = aParams -> oy;
+			p.la = aParams -> la;
+		}
+
+		const int rc = avirhip_lancir_resize_planes( h, SrcViews,
+			AVIRHIP_MEM_VIEWS, SrcWidth, SrcHeight, (void*) NewViews,
+			AVIRHIP_MEM_VIEWS, NewWidth, NewHeight, PlaneCount, 0, 0, &p,
+			dt< Tin > :: v, dt< Tout > :: v, stream );
+
+		if( rc == AVIRHIP_ENOMEM )
+		{
+			throw std::bad_alloc();
+		}
+
+		if( rc < 0 )
+		{
+			throw std::runtime_error( std::string(
+				"avir::CLancIR::resizeImagePlanes: " ) + avirhip_last_error() );
+		}
+
+		return( rc );
+	}
+
 private:
 	avirhip_lancir* h;
 };

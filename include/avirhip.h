@@ -139,6 +139,19 @@ typedef enum avirhip_dtype {
 #define AVIRHIP_MEM_HOST 0
 #define AVIRHIP_MEM_DEVICE 1
 #define AVIRHIP_MEM_AUTO 2 /* ask the HIP runtime (hipPointerGetAttributes) */
+/* Planar calls only: `src` / `dst` is a HOST array of n_planes
+ * avirhip_plane_view, one per plane ("Plane views" below). */
+#define AVIRHIP_MEM_VIEWS 3
+#define AVIRHIP_HAS_VIEWS 1
+
+/* One plane of a planar call where it lies in DEVICE memory: element (r, c) of
+ * the plane is base[ r * row_pitch + c * elem_stride ], in elements of the
+ * side's type. */
+typedef struct avirhip_plane_view {
+	void*     base;        /* device pointer to element (0,0) of the plane */
+	long long row_pitch;   /* elements between rows; 0: the call's own rule */
+	long long elem_stride; /* elements between neighbours in a row; 0 or 1: dense */
+} avirhip_plane_view;      /* 24 bytes */
 
 /* ---------------------------------------------------------------------
  * AVIR plan description: a faithful, flattened mirror of the reference's
@@ -704,6 +717,52 @@ int avirhip_lancir_get_plan(avirhip_lancir* l, int src_w, int src_h,
  * the error-diffusion ditherer, fpclass_float4 and fpclass_def<double>
  * objects, other bases and filters too long for its tiles run the plan's own
  * road once per plane -- the same bits ("CImageResizer planes").
+ *
+ * Plane views. `src_mem` / `dst_mem` may be AVIRHIP_MEM_VIEWS, each side on its
+ * own: that side's pointer is then a HOST array of n_planes avirhip_plane_view
+ * and its plane-stride argument must be 0 (else AVIRHIP_EINVAL). One HWC RGB
+ * image is three views { img + c, W * 3, 3 }; a channels-last N x C x H x W
+ * batch is N * C views; a list of separately allocated planes is one view
+ * each. The array is read inside the call: the caller may overwrite or free
+ * it as soon as the call returns, whatever the stream still has to do.
+ *   Pitch.    With E = max( elem_stride, 1 ): row_pitch 0 means, for E == 1, the
+ *             pitch the call has without views (SrcSSize / NewSSize /
+ *             SrcScanlineSize, the width where that is < 1; the tight result
+ *             row of CImageResizer), and for E > 1 width * E -- the tight row
+ *             of an interleaved image.
+ *   Result.   Unchanged: plane i equals, bit for bit, the ElCount = 1 /
+ *             ElCountIO = 1 call of the reference on the elements of view i
+ *             gathered into a tight plane. CLancIR's integer rounding goes by
+ *             the element's position j in its row of new_w elements, not by
+ *             its address.
+ *   Untouched bytes. Nothing but the new_w x new_h elements of each result
+ *             view is written: not the elements between strided neighbours
+ *             (the X byte of an RGBX result), not between rows.
+ *   Validation, host arithmetic only and before any device call, each
+ *             AVIRHIP_EINVAL with a message: a null base; a negative pitch or
+ *             stride; where height > 1, row_pitch < ( width - 1 ) * E + 1; a
+ *             base that is no multiple of the element size; a view that
+ *             leaves the address space.
+ *   Overlap.  Source views may overlap each other freely. The byte span of a
+ *             result view must not meet the byte span of any source view. Two
+ *             result views whose byte spans meet are accepted only as
+ *             interleaved planes: the same row_pitch P and elem_stride E,
+ *             P % E == 0, bases d elements apart with d % E != 0 -- their
+ *             elements are then disjoint. Where height is 1 the pitch
+ *             addresses nothing and P is not compared. Any other meeting: AVIRHIP_EINVAL.
+ *   Zero-sized source or destination and the front ends' parameter errors
+ *             behave as above, view by view.
+ *   Memory.   Bases are device pointers; host pixel memory behind a view is
+ *             not supported. The other side of such a call, where it has no
+ *             views, keeps its plane stride rule and must be device memory at
+ *             a base that is a multiple of the element size.
+ * Views run in the same ONE launch (k_lancp / k_avirp read each plane's base,
+ * pitch and stride from a table the call copies to the device). Where the
+ * kernel declines (see above), a view that is not a tight plane at the plan's
+ * pitch is gathered into / scattered from a per-call device buffer (allocated
+ * and freed in the order of `stream`: no wait for the device), one plane
+ * at a time, around the plan's own road; the scatter writes the plane's
+ * elements only.
  *
  * Plan level: `plan` is a CLancIR or a CImageResizer plan of one channel; any
  * other channel count returns AVIRHIP_EUNSUPPORTED. Returns AVIRHIP_OK or an
